@@ -14,16 +14,20 @@ region ends when every .drc / .ktx2 byte is in host memory.
                                                                       # frames, split over the ranks by shard.plan; a step = the job
 
 `value` is quoted with the inputs resident in HBM when the timed region starts - the bench contract's rule for this tier ("if the boundary hands over
-host buffers, note the PCIe-inclusive rate - it is never `value`").  The SAME line carries, as top-level keys, what the SURVEY §8(d) boundary gives
+host buffers, note the PCIe-inclusive rate - it is never `value`").  With `--full` the SAME line carries, as top-level keys, what the SURVEY §8(d) boundary gives
 (`survey_8d_boundary_frames_per_s`: pinned / pageable host memory through the blocking and the enqueue forms, and what the link allows for the bytes
 the ABI takes) and BASELINE configs[2]'s own 300-frame job (`configs2_job_300_frames_per_s`).
 
 `--gpus N` is the rank count: without a launcher `python bench.py --gpus N` starts its N ranks itself (torch.distributed.run on 127.0.0.1); under one,
 WORLD_SIZE and the process group's size must equal it or the run exits non-zero.  The only collective is the final 32-byte-per-rank manifest gather
 (SURVEY §8e), over RCCL.
-On one GPU the line also carries `variants` (never `value`): the same path on the SURVEY §8(d) boundary (host buffers), as small
-jobs (150 / 300 / 1200 frames -> the 8-GPU projection of configs[3]), on a scan-like storage order, and the decode path
-(configs[4]); `--no-variants` skips them.
+A plain run sets up, warms up, times `--steps` steps and prints the line (`value`, `ms_per_step`, the kernel groups and `roofline` of
+the timed steps).  `--full` adds what the headline does not need, all after the timed region: the parity check of the step's bytes
+against the CPU oracle (`parity`; a mismatch fails the run), the quality gates (`quality`), the CPU oracle's own rate (`cpu_baseline`,
+`--no-cpu-baseline` skips it), at N > 1 the strong job (`strong_configs3`), and on one GPU `variants` (never `value`): the same path
+on the SURVEY §8(d) boundary (host buffers), as small jobs (150 / 300 / 1200 frames -> the 8-GPU projection of configs[3]), on a
+scan-like storage order, and the decode path (configs[4]); `--no-variants` skips them.
+`--dump-outputs DIR` writes what the last timed step handed its caller (rank 0's .drc / .ktx2 files) as .npy arrays: see dump_outputs().
 """
 import argparse
 import ctypes as C
@@ -33,6 +37,7 @@ import sys
 import threading
 import time
 
+T_START = time.perf_counter()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "universal-volumetric_amd"))
 # One hardware queue per stream: the runtime's default is 4 hardware queues per process, and streams that share one run one after the
@@ -62,13 +67,16 @@ def main():
     ap.add_argument("--connectivity", choices=["distinct", "identical"], default="distinct",
                     help="distinct (headline): every synthetic frame has its own connectivity and vertex count, like a capture's frames; identical (DIAGNOSTIC): "
                          "the frames share one index array (an animated mesh of fixed topology) and the lane-per-walker kernels run in lock step")
-    ap.add_argument("--parity-frames", type=int, default=8, help="frames of the timed step whose bytes are compared with the CPU oracle's after the timed region (0: skip)")
+    ap.add_argument("--parity-frames", type=int, default=8, help="with --full: frames of the timed step whose bytes are compared with the CPU oracle's after the timed region (0: skip)")
     ap.add_argument("--shared-inputs", action="store_true", help="DIAGNOSTIC: all frames read the same --distinct input buffers / one texture segment")
     ap.add_argument("--geo-streams", type=int, default=1, help="geometry contexts (HIP streams); frames of a step are split evenly between them")
     ap.add_argument("--mesh-order", choices=["lattice", "shuffled"], default="lattice", help="DIAGNOSTIC 'shuffled': seeded permutation of faces and values (scan-like storage order, no cache-line locality between consecutive faces)")
     ap.add_argument("--tex-streams", type=int, default=1, help="texture contexts (HIP streams) fed by host threads")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-variants", action="store_true", help="skip the workload variants reported next to the headline on one GPU")
+    ap.add_argument("--full", action="store_true", help="after the timed region also run the parity check against the CPU oracle, the quality gates, the CPU baseline, "
+                                                        "the strong job (N > 1) and the workload variants (one GPU); a plain run reports the timed steps alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed (rank 0) to DIR/<name>.npy: see dump_outputs()")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-variants", action="store_true", help="with --full: skip the workload variants reported next to the headline on one GPU")
     ap.add_argument("--traverse-vbits-l2", type=int, default=0, help="LDS walkers (small batches): 1 = attribute traversers keep their vertex bitmap in L2")
     ap.add_argument("--tex-priority", type=int, default=1, help="1: texture contexts use a high-priority HIP stream")
     ap.add_argument("--geo-priority", type=int, default=0, help="1: geometry contexts use a high-priority HIP stream (diagnostic)")
@@ -145,7 +153,7 @@ def main():
         F = args.frames_per_step
         assert F % B == 0
         nseg = F // B
-    variants_on = world == 1 and not args.no_variants and (not args.only or os.environ.get("UVOL_VARIANTS_WITH_ONLY") == "1") and not args.host_inputs and not strong and args.mesh_order == "lattice"
+    variants_on = args.full and world == 1 and not args.no_variants and (not args.only or os.environ.get("UVOL_VARIANTS_WITH_ONLY") == "1") and not args.host_inputs and not strong and args.mesh_order == "lattice"
     F_alloc = max(F, 1)
 
     # ---- synthetic frames (seeded), uploaded once; inputs are resident in HBM when timing starts ----
@@ -155,6 +163,7 @@ def main():
     if args.mesh_order == "shuffled":
         meshes_h = [synth.shuffle_mesh(m, seed=100 + k) for k, m in enumerate(meshes_h)]
     tex_h = synth.texture_sequence(B, size=args.tex_size, seed=0)
+    t_synth = time.perf_counter()
     keep = []
     dev_meshes = []
     frame_t = []
@@ -348,8 +357,10 @@ def main():
         torch.cuda.synchronize()
 
     main_job = Job(F, host=args.host_inputs, host_enqueued=args.host_enqueued, pinned=args.host_pinned)
+    t_setup = time.perf_counter()
     if args.warmup:
         main_job.steps(args.warmup)
+    t_warm = time.perf_counter()
     bg = {"stop": False, "bytes": 0, "t": 0.0}
     if args.background != "off":
         nb = (256 << 20) if args.background == "h2d_256m" else (16 << 20)
@@ -387,6 +398,8 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=cdev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt[0])
+    if args.dump_outputs and rank == 0:                        # (before anything below runs the contexts again)
+        dump_outputs(args.dump_outputs, out)
 
     drc_len = sum(len(x) for x in out["drc"]) / max(F, 1)
     ktx_len = sum(len(x) for x in out["ktx2"]) / max(F, 1)
@@ -395,7 +408,7 @@ def main():
     # ONE 1200-frame sequence split over the ranks by whole texture segments, each rank's share one blocking job, the 32-byte manifest
     # gather inside the timed region - so that one driver line per N carries both curves
     strong_extra = None
-    if world > 1 and not strong and not args.host_inputs and not args.only:
+    if args.full and world > 1 and not strong and not args.host_inputs and not args.only:
         TF = args.strong_frames
         _, Fs, _, nsegs = shard.plan(TF, B, world, rank)
         if 0 < Fs <= F:
@@ -469,8 +482,9 @@ def main():
                                     "ops_per_launch": mfma_grp["algo_bytes"] / max(1, mfma_grp["launches"]), "dtype": "i8 x i8 -> i32"}
         if args.background != "off":
             res["background"] = {"kind": args.background, "GBps": bg["bytes"] / max(bg["t"], 1e-9) / 1e9}
-        res["quality"] = quality_gates(geos[0], texs[0], out, meshes_h[0], tex_h, B) if not args.only and F else None
-        if args.parity_frames > 0 and F and not args.host_inputs:
+        if args.full:
+            res["quality"] = quality_gates(geos[0], texs[0], out, meshes_h[0], tex_h, B) if not args.only and F else None
+        if args.full and args.parity_frames > 0 and F and not args.host_inputs:
             res["parity"] = parity_check(out, meshes_h, tex_h, args.parity_frames, args.only, args.mesh_order)
             res["parity_checked_frames"] = res["parity"].get("geometry_frames_equal_to_oracle", 0)
         if strong_extra:
@@ -490,9 +504,11 @@ def main():
                                                           "link_bound": hi.get("link", {}).get("frames_per_s_the_link_allows")}
             if "job_300" in res["variants"]:
                 res["configs2_job_300_frames_per_s"] = res["variants"]["job_300"]["frames_per_s"]
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             res["cpu_baseline"] = cpu_baseline(meshes_h[0], tex_h, B)
         print(json.dumps(res), flush=True)
+        print("[bench] %.1f s from start to the line: set-up %.1f s (synthetic inputs %.1f s), warm-up %.1f s, timed steps %.1f s, after them %.1f s"
+              % (time.perf_counter() - T_START, t_setup - T_START, t_synth - T_START, t_warm - t_setup, dt, time.perf_counter() - t0 - dt), file=sys.stderr, flush=True)
         if (res.get("parity") or {}).get("mismatches"):          # a fast line whose bytes differ from the reference algorithm's is not a result
             failed = 3
     for c in geos + texs:
@@ -639,6 +655,36 @@ def run_variants(v, args, Job, set_profiling, frame_t, meshes_h, tex_h, out, geo
         v["decode_error"] = repr(e)
     v.pop("in_progress", None)
     return v
+
+
+def dump_outputs(d, out, budget=60_000_000):
+    """--dump-outputs DIR: what the last timed step handed its caller - one .drc per geometry frame (`drc`), one .ktx2 per texture
+    segment (`ktx2`) - so that two builds can be compared output for output (the inputs are seeded: equal arguments, equal inputs).
+    Per stream: `<s>_lengths` and `<s>_crc32` (float64, every file of the step) and the bytes of a fixed, seeded sample of whole files
+    (`<s>_sample_bytes`, float32, files in the order of `<s>_sample_index`, file k at `<s>_sample_offsets[k]`); 64 MB in all at most."""
+    import zlib
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    streams = [(s, out.get(s) or []) for s in ("drc", "ktx2")]
+    streams = [(s, files) for s, files in streams if files]
+    total = 0
+    share = (budget - sum(4 * 8 * (len(files) + 1) for _, files in streams)) // (4 * max(1, len(streams)))     # sampled bytes per stream
+    for s, files in streams:
+        meta = {"lengths": np.array([len(x) for x in files], np.float64), "crc32": np.array([zlib.crc32(x) for x in files], np.float64)}
+        pick, used = [], 0
+        for i in np.random.default_rng(0).permutation(len(files)):      # a prefix of one seeded order of the files
+            if used + len(files[i]) > share:
+                break
+            pick.append(int(i)); used += len(files[i])
+        pick.sort()
+        meta["sample_index"] = np.array(pick, np.float64)
+        meta["sample_offsets"] = np.cumsum([0] + [len(files[i]) for i in pick]).astype(np.float64)
+        meta["sample_bytes"] = np.concatenate([np.frombuffer(files[i], np.uint8) for i in pick] or [np.zeros(0, np.uint8)]).astype(np.float32)
+        for k, a in meta.items():
+            np.save(os.path.join(d, "%s_%s.npy" % (s, k)), a)
+            total += a.nbytes
+    assert total <= budget, total
+    print("[bench] outputs of the last timed step: %s (%.1f MB)" % (d, total / 1e6), file=sys.stderr, flush=True)
 
 
 def parity_check(out, meshes_h, tex_h, n_check, only, mesh_order):

@@ -8,7 +8,7 @@ for p in (os.path.join(ROOT, "oracle"), os.path.join(ROOT, "universal-volumetric
         sys.path.insert(0, p)
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-REF_OUT = "/root/reference/example/public/liam/output"
+REF_OUT = os.path.join(GOLDEN, "reference_output")      # the upstream example's recorded encoder outputs (250 .drc, 50 .ktx2)
 
 
 def pytest_configure(config):

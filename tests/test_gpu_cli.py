@@ -106,7 +106,7 @@ def test_bench_gpus_2_runs_two_ranks(tmp_path):
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env["UVOL_BENCH_ONE_DEVICE"] = "1"
     argv = ["--gpus", "2", "--steps", "2", "--warmup", "1", "--frames-per-step", "40", "--strong-frames", "60", "--segs", "40", "--rings", "21",
-            "--tex-size", "256", "--distinct", "8", "--parity-frames", "4", "--no-cpu-baseline"]
+            "--tex-size", "256", "--distinct", "8", "--parity-frames", "4", "--no-cpu-baseline", "--full"]
     import sys
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]

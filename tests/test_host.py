@@ -51,7 +51,6 @@ def test_config_with_comments_and_template(H):
     assert H.uvolh_check_config(t.encode()).decode() == "Path to Geometry data is not specified"
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OUT), reason="/root/reference only exists in the build container")
 def test_check_total_frames_on_reference_fixture(H):
     g = G["check_total_frames_fixture"]
     r = json.loads(H.uvolh_check_total_frames(os.path.join(REF_OUT, "geometry_draco", "#####.drc").encode(),

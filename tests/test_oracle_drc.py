@@ -48,7 +48,6 @@ def test_decoder_on_committed_fixtures(oracle, name):
     _check_file(oracle, open(os.path.join(GOLDEN, name), "rb").read(), GOLD["files"][name])
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_OUT), reason="/root/reference only exists in the build container")
 def test_decoder_on_all_250_reference_fixtures(oracle):
     agg = ""
     for name in sorted(GOLD["files"]):

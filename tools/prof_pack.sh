@@ -11,8 +11,8 @@ if has tests; then
   (timeout 600 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | tail -2) >> $O/gpu_tests.log
 fi
 if has bench; then
-  timeout 1200 python bench.py > $O/bench.json 2> $O/bench.err
-  timeout 900 python bench.py --no-cpu-baseline > $O/bench_run2.json 2>> $O/bench.err
+  timeout 1200 python bench.py --full > $O/bench.json 2> $O/bench.err
+  timeout 900 python bench.py --full --no-cpu-baseline > $O/bench_run2.json 2>> $O/bench.err
 fi
 if has rocprof; then
   timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt -o bench -- python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-variants > $O/bench_under_rocprof.json 2>> $O/bench.err
@@ -35,5 +35,5 @@ if has host; then
 fi
 # the N > 1 code path on this one-GPU box: `python bench.py --gpus 2` launches its two ranks itself, both drive device 0, the gather goes over gloo
 if has ranks; then
-  UVOL_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --gpus 2 --frames-per-step 1000 --strong-frames 1200 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_one_device.json 2>> $O/bench.err
+  UVOL_BENCH_ONE_DEVICE=1 timeout 900 python bench.py --full --gpus 2 --frames-per-step 1000 --strong-frames 1200 --steps 3 --warmup 1 --no-cpu-baseline > $O/bench_2ranks_one_device.json 2>> $O/bench.err
 fi
