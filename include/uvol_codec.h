@@ -44,7 +44,8 @@ typedef struct uvol_params {
   int32_t q_position_attr;          /* Q_POSITION_ATTR,         default 11 */
   int32_t q_texture_attr;           /* Q_TEXTURE_ATTR,          default 10 */
   int32_t q_normal_attr;            /* Q_NORMAL_ATTR,           default 8  */
-  int32_t q_generic_attr;           /* Q_GENERIC_ATTR,          default 8 (accepted, unused: no generic attribute on this ABI) */
+  int32_t q_generic_attr;           /* Q_GENERIC_ATTR,          default 8 (accepted, numerically inert as in stock draco_encoder: the one generic attribute, the
+                                       material id of uvol_encode_mesh_batch_mat, is an integer attribute and Draco quantises float attributes only) */
   int32_t draco_compression_level;  /* DRACO_COMPRESSION_LEVEL 0..10, default 7.  0 = sequential connectivity + difference predictor (stock draco_encoder's choice at
                                        this level); 1..10 are encoded with the level-7 tool set (valence edgebreaker; the level itself is not part of the bitstream) */
   int32_t ktx2_batch_size;          /* KTX2_BATCH_SIZE (mandatory in the reference) = layers per .ktx2 */
@@ -184,6 +185,29 @@ int uvol_encode_mesh_batch_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n,
                                  uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
 int uvol_encode_mesh_batch_dev_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n,
                                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
+
+/* ---- material ids: the OBJ `usemtl` attribute (additive: uvol_abi_version stays 1) ----
+ * Stock draco_encoder adds a fourth attribute to every OBJ that has a `usemtl` line: GENERIC, uint8, one component, the index of the face's
+ * material (every recorded .drc of the reference carries it).  uvol_mesh is passed in arrays, so the ids travel in a parallel array:
+ * face_material: NULL, or n entries; face_material[i]: NULL (frame i is encoded exactly as by uvol_encode_mesh_batch*) or meshes[i].n_faces
+ * bytes, one material id per INPUT face, in host or device memory like the mesh's own arrays (inputs_on_device).  The attribute is written as
+ * Draco writes it while every vertex has ONE material - single-material frames, and frames whose materials follow connected components: a
+ * vertex attribute on the base corner table, parallelogram prediction, wrap transform.  A frame in which two materials meet at a shared
+ * vertex (an interior material seam, which Draco codes as a corner attribute with a table of its own) gets status[i] = UVOL_E_UNSUPPORTED,
+ * uvol_last_error names it, and the other frames of the batch are not affected: encode that frame without materials.  With
+ * DRACO_COMPRESSION_LEVEL 0 (sequential connectivity) a call that passes any ids is refused as a whole (UVOL_E_UNSUPPORTED).  Host ids are
+ * uploaded through the library's staging buffers; uvol_encode_mesh_batch_dev_out has no such form. */
+size_t uvol_mesh_bound_mat(const uvol_mesh *m);      /* upper bound of the .drc of a frame with material ids */
+int uvol_encode_mesh_batch_mat(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, int inputs_on_device,
+                               uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
+/* enqueue form: the contract of uvol_encode_mesh_batch_async (the face_material ARRAY is copied, the ids belong to the call until uvol_sync) */
+int uvol_encode_mesh_batch_mat_async(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, int inputs_on_device,
+                                     uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
+/* As uvol_parse_obj_batch_dev, plus face_material_dev_out[i] = device pointer to one byte per fanned triangle (in the context's slot, like the
+ * mesh's arrays), or NULL when the file has no `usemtl` line.  Ids are handed out by first appearance of the name, from 0; faces ahead of the
+ * first `usemtl` take id 0; `mtllib` files are not read; a file with more than 256 names loses the attribute (stock switches to uint16). */
+int uvol_parse_obj_batch_dev_mat(uvol_ctx *ctx, const uint8_t *const *obj_text, const size_t *lens, int n, int slot,
+                                 uvol_mesh *meshes_out, const uint8_t **face_material_dev_out, int *status);
 
 /* Replaces one `basisu -ktx2 -tex_type video` process (scripts/Encoder.py:290-292):
  * n_layers RGBA8 images (width*height*4 bytes each, top row first as a PNG decoder yields them)
@@ -328,6 +352,13 @@ int uvol_decode_mesh_batch(uvol_ctx *ctx, const uint8_t *const *drc, const size_
  * (a renderer's vertex buffers, or uvol_encode_mesh_batch_dev[_out] re-encoding them) reads without a host round trip.  The .drc
  * files themselves are host memory; counts come back in `out`. */
 int uvol_decode_mesh_batch_dev(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, uvol_decoded_mesh *out, int *status);
+
+/* As uvol_decode_mesh_batch (outputs_on_device = 0) / uvol_decode_mesh_batch_dev (1), plus the material ids: face_material (may be NULL)
+ * holds n entries, face_material[i] = NULL or out[i].cap_faces bytes (host / device memory like the arrays of `out`) that receive one id per
+ * face, in the face order of idx_pos; has_material[i] (may be NULL) = 1 when the file carries a GENERIC uint8 1-component vertex attribute,
+ * else 0 and the buffer is left alone (a generic attribute of another shape decodes as it always did and reports no material). */
+int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
+                               uvol_decoded_mesh *out, uint8_t *const *face_material, int *has_material, int *status);
 
 /* ---- measurement hooks (bench.py / rocprof cross-check) ---- */
 /* When enabled, every kernel group is bracketed by hipEvents on the ctx stream. */

@@ -34,10 +34,18 @@ for t in ("bc1", "bc3", "etc2_rgba", "bc7"):                    # every block ta
     cd.transcode_texture_segments_status([k1, k2], t, shape=(40, 40, 2)); cd.transcode_texture_segments_status([k2], t, shape=(36, 36, 2))
 c0 = uvol.Codec(lib_path=lib, DRACO_COMPRESSION_LEVEL=0); g0 = c0.encode_mesh_batch(ms[:3]); c0.decode_mesh_batch(g0); c0.close()
 cu = uvol.Codec(lib_path=lib, uastc=1); ku = cu.encode_texture_segment(ta); cu.decode_texture_segments([ku]); cu.close()
+# material ids (GENERIC uint8): carried through dropped / permuted faces, per-vertex values and the seam test, the predictor, the extra
+# rANS / rabs streams, the refused frame, the decoder's per-face step and the `usemtl` records of the device OBJ parser
+import pathlib, tempfile
+import material_cases as MC
+mat_streams = MC.run_values(o, cd); MC.run_shuffled(o, cd); MC.run_refusal(o, cd, lib_path=lib)
+MC.run_decoder(o, cd, MC.HostMem(), mat_streams[:2])
+with tempfile.TemporaryDirectory() as td:
+    MC.run_ingest(o, cd, MC.HostMem(), pathlib.Path(td))
 # corrupted decoder inputs: bit flips, truncations, overwritten words - a clean error or a decoded result, never an out-of-bounds access
 rng = np.random.default_rng(5)
 outcomes = {}
-for kind, data, first in (("drc", files[0], 11), ("drc_std", files[1], 11), ("drc_seq", files[2], 11), ("ktx2", k1, 80), ("ktx2_alpha", k2, 80), ("uastc", ku, 80)):
+for kind, data, first in (("drc", files[0], 11), ("drc_mat", mat_streams[2], 11), ("drc_std", files[1], 11), ("drc_seq", files[2], 11), ("ktx2", k1, 80), ("ktx2_alpha", k2, 80), ("uastc", ku, 80)):
     ok = bad = 0
     for it in range(ncorrupt):
         b = bytearray(data); mode = it % 3

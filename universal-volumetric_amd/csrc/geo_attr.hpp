@@ -123,6 +123,56 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_pred_pos(GeoJob *jobs) {
   for (int k = 0; k < 3; k++) J.sym_pos[3 * p + k] = g_sym_of(g_wrap_corr(J.wrap_lo[0], J.wrap_hi[0], o[k], pred[k]));
 }
 
+// ------------------------------------------------------------------------------------------------
+// Material attribute (GENERIC uint8, one component, a vertex attribute of the BASE table).  The ids arrive per face; the file holds one
+// per base-table vertex, which exists only while every corner of a vertex carries the same id.  Pass A (thread per stored corner)
+// hands its face's id to the corner's vertex - several writers, any of them wins: no atomics on random lines - and reduces the ids'
+// range for the wrap transform; pass B reads the winner back and raises the frame's flag when its own id differs: two materials meet
+// at that vertex (an interior material seam, which Draco codes as a corner attribute: refused, k_stream_setup).
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(UVOL_BLOCK) k_mat_vert(GeoJob *jobs, int pass) {
+  GeoJob &J = jobs[blockIdx.y];
+  const bool on = J.status == 0 && J.has_mat;
+  const uint32_t c = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  const bool live = on && c < J.nc;
+  uint32_t lo = 0xffffffffu, hi = 0;
+  if (live) {
+    const uint32_t m = J.fmat[c / 3]; const int v = geo_vt(J)[c];
+    if (pass == 0) { J.vmat[v] = (uint8_t)m; lo = hi = m; }
+    else if (J.vmat[v] != m) J.mat_seam = 1;
+  }
+  if (pass != 0) return;
+  for (int d = 32; d >= 1; d >>= 1) { const uint32_t l2 = __shfl_xor(lo, d), h2 = __shfl_xor(hi, d); lo = l2 < lo ? l2 : lo; hi = h2 > hi ? h2 : hi; }
+  // (a wave whose range lies inside what the frame already holds adds nothing: after the first waves no atomic leaves a CU; 9 k waves per
+  // frame on two words: this pass took 50.8 ms per 2560 frames with unconditional atomics, 16.7 ms so - profiles/r07_material_attribute.json)
+  if ((threadIdx.x & 63) == 0 && lo <= hi) { if (lo < J.mat_lo) atomicMin(&J.mat_lo, lo); if (hi > J.mat_hi) atomicMax(&J.mat_hi, hi); }
+}
+// Residuals of the material ids (thread per entry of the base table, as k_pred_pos with one component): Draco's parallelogram rule with
+// the same neighbour-availability test, the previous entry otherwise (0 for entry 0), wrap transform over the frame's [min id, max id].
+__global__ void __launch_bounds__(UVOL_BLOCK) k_pred_mat(GeoJob *jobs) {
+  JOB_OR_RETURN;
+  if (!J.has_mat) return;
+  const uint32_t p = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (p >= J.ne[0]) return;
+  const int32_t *v2d = J.v2d[0], *vt = geo_vt(J);
+  const int ci = J.order[0][p];
+  const int own = J.vmat[vt[ci]];
+  long long pred = 0;
+  if (p > 0) {
+    bool have = false;
+    const int oci = J.opp[ci];
+    if (oci >= 0) {
+      const int fo = 3 * (oci / 3), j = oci - fo;
+      const uvol_s3 v3 = *reinterpret_cast<const uvol_s3 *>(vt + fo);
+      const int vv[3] = { v3.x, v3.y, v3.z };
+      const uint32_t a = (uint32_t)v2d[vv[j]], bn = (uint32_t)v2d[vv[(j + 1) % 3]], bp = (uint32_t)v2d[vv[(j + 2) % 3]];
+      if (a < p && bn < p && bp < p) { pred = (long long)J.vmat[vv[(j + 1) % 3]] + J.vmat[vv[(j + 2) % 3]] - J.vmat[vv[j]]; have = true; }
+    }
+    if (!have) pred = J.vmat[vt[J.order[0][p - 1]]];
+  }
+  J.sym_mat[p] = g_sym_of(g_wrap_corr((int)J.mat_lo, (int)J.mat_hi, own, pred));
+}
+
 __global__ void __launch_bounds__(UVOL_BLOCK) k_pred_uv(GeoJob *jobs) {
   JOB_OR_RETURN;
   int i = -1; for (int k = 0; k < J.nad; k++) if (J.att_kind[k] == 0) i = k;

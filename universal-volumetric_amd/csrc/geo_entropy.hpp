@@ -203,7 +203,7 @@ __global__ void __launch_bounds__(64) k_entropy_encode(GeoJob *jobs, int dbg) {
   } else {
     RabsStream &B = J.rb[blockIdx.y - GEO_NSTREAM];
     __syncthreads();
-    if (!ok) return;
+    if (!ok || !B.buf) return;                                         // (no buffer: the material seam stream of a frame without materials)
     const uint32_t n = B.n; const uint64_t total = n ? n : 1;
     const uint32_t p0raw = (uint32_t)(((double)B.zeros / (double)total) * 256.0 + 0.5);
     uint32_t p0 = p0raw < 255 ? p0raw : 255; if (p0 == 0) p0 = 1;
@@ -216,12 +216,13 @@ __global__ void __launch_bounds__(64) k_entropy_encode(GeoJob *jobs, int dbg) {
     const uint32_t m1 = UVOL_READLANE(r1.x, 0), s1 = UVOL_READLANE(r1.y, 0), m0 = UVOL_READLANE(r0.x, 0), s0 = UVOL_READLANE(r0.y, 0);
     const uint32_t a1 = (p == 1 ? 255u : 0u), a0 = p + (p0 == 1 ? 255u : 0u);
     const uint32_t lim1 = 4096u * p, lim0 = 4096u * p0, mu1 = 256u - p, mu0 = 256u - p0;
-    uint32_t nxt = (lane < n && B.bits[n - 1 - lane] != 0) ? 1u : 0u;
+    const bool all0 = B.bits == nullptr;                               // a stream of zero bits needs no array (the material attribute's seams)
+    uint32_t nxt = (!all0 && lane < n && B.bits[n - 1 - lane] != 0) ? 1u : 0u;
     for (uint32_t hi = n; hi > 0;) {
       const uint32_t cnt = hi < 64 ? hi : 64;
       const unsigned long long bm = __ballot(nxt != 0);                // bit j = j-th bit from the end
       hi -= cnt;
-      nxt = (lane < hi && B.bits[hi - 1 - lane] != 0) ? 1u : 0u;        // next chunk's read overlaps this chunk's serial loop
+      nxt = (!all0 && lane < hi && B.bits[hi - 1 - lane] != 0) ? 1u : 0u;        // next chunk's read overlaps this chunk's serial loop
       for (uint32_t j = 0; j < cnt;) {                                  // runs of zeros in a tight loop with constant operands
         const unsigned long long rest = bm >> j;
         uint32_t run = rest ? (uint32_t)(__ffsll((long long)rest) - 1) : 64u; if (run > cnt - j) run = cnt - j;
@@ -410,6 +411,36 @@ __device__ inline void rabs_encode_lane(GeoJob &J, RabsStream &B, uint32_t *lds_
   B.buf[8 - vl - 1] = (uint8_t)p0;
   B.off = 8 - vl - 1; B.len = 1 + vl + w;
 }
+// The material attribute's seam stream: B.n zero bits and no array (a vertex attribute has no seams).  The same coder with the constants of
+// an all-zero stream (p0 = 255), nothing to fetch; a function of its own - not inlined - so that the code of rabs_encode_lane, which every
+// frame runs, is what it was.  A frame without materials has no buffer for it and leaves at once.
+__device__ __attribute__((noinline)) void rabs_encode_zeros_lane(GeoJob &J, RabsStream &B, uint32_t *lds_lane) {
+  if (!B.buf) return;
+  const uint32_t n = B.n, p0 = 255, p = 1;
+  SByteOut O; O.init(B.buf + 8, B.cap - 80, lds_lane);
+  uint32_t st = 4096;
+  const uint2 r0 = g_recip(p0);
+  const uint32_t a0 = p, lim0 = 4096u * p0, mu0 = 256u - p0;
+  for (uint32_t i = n; i; ) {
+    i--;
+    { const bool c_ = st >= lim0; O.put_n(st, c_ ? 1u : 0u); st = c_ ? st >> 8 : st; }
+    const uint32_t q = __umulhi(st, r0.x) >> r0.y;
+    st = st + a0 + q * mu0;
+    if ((i & 15u) == 0) O.group_end();
+  }
+  uint32_t w = O.bytes();
+  if (w + 3 > O.cap) { J.status = -33; return; }
+  O.flush();
+  uint8_t *pay = B.buf + 8;
+  st -= 4096;
+  if (st < (1u << 6)) pay[w++] = (uint8_t)st;
+  else if (st < (1u << 14)) { const uint32_t v = (1u << 14) + st; pay[w++] = v & 255; pay[w++] = (v >> 8) & 255; }
+  else { const uint32_t v = (2u << 22) + st; pay[w++] = v & 255; pay[w++] = (v >> 8) & 255; pay[w++] = (v >> 16) & 255; }
+  const uint32_t vl = g_varint_len(w);
+  g_put_varint(B.buf + 8 - vl, w);
+  B.buf[8 - vl - 1] = (uint8_t)p0;
+  B.off = 8 - vl - 1; B.len = 1 + vl + w;
+}
 // grid (frame blocks, stream); lanes of a wave = the same stream of W consecutive frames
 __global__ void __launch_bounds__(64) k_entropy_simt(GeoJob *jobs, int n, int W) {
   UVOL_DYN_SMEM(uint32_t, lds);                                         // SB_STRIDE dwords per lane: the coders' output staging
@@ -420,6 +451,8 @@ __global__ void __launch_bounds__(64) k_entropy_simt(GeoJob *jobs, int n, int W)
   GeoJob &J = jobs[j];
   if (J.status != 0) return;
   const int t = (int)blockIdx.y;
-  if (t < GEO_NSTREAM) rans_encode_lane(J, J.rs[t], lds + lane * SB_STRIDE); else rabs_encode_lane(J, J.rb[t - GEO_NSTREAM], lds + lane * SB_STRIDE);
+  if (t < GEO_NSTREAM) rans_encode_lane(J, J.rs[t], lds + lane * SB_STRIDE);
+  else if (t == GEO_NSTREAM + GEO_RB_MAT) rabs_encode_zeros_lane(J, J.rb[GEO_RB_MAT], lds + lane * SB_STRIDE);
+  else rabs_encode_lane(J, J.rb[t - GEO_NSTREAM], lds + lane * SB_STRIDE);
 }
 

@@ -190,6 +190,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_relabel_faces(GeoJob *jobs) {
   *reinterpret_cast<uvol_s3 *>(J.cp + 3 * (size_t)s) = a; *reinterpret_cast<uvol_s3 *>(J.cu + 3 * (size_t)s) = b; *reinterpret_cast<uvol_s3 *>(J.cn + 3 * (size_t)s) = c;
   const uint32_t co = J.cidx[f];
   J.forig[s] = (int32_t)co; J.s_of_o[co] = (int32_t)s;
+  if (J.has_mat) { J.fmat_s[s] = J.imat[f]; if (s == 0) J.fmat = J.fmat_s; }      // the material id moves with its face
 }
 
 // per input face: canonical ids, keep flag, index validation
@@ -239,6 +240,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_compact_faces(GeoJob *jobs, int 
     if (!al1) *reinterpret_cast<uvol_s3 *>(J.cu + 3 * (size_t)pos) = b;
     if (!al2) *reinterpret_cast<uvol_s3 *>(J.cn + 3 * (size_t)pos) = c;
   }
+  if (live && v && J.has_mat && !all_kept && !J.compact) J.fmat_s[pos] = J.imat[f];      // a dropped face takes its material id with it (compact layout: no face is dropped, no copy exists)
+
   if (blockIdx.x == 0 && threadIdx.x == 0 && J.status == 0) {
     uint32_t nf = J.bsum[uvol_blocks_dev(J.nf_in)];
     J.nf = nf; J.nc = 3 * nf;
@@ -247,6 +250,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_compact_faces(GeoJob *jobs, int 
     if (al0) J.cp = reinterpret_cast<int32_t *>(const_cast<uint32_t *>(J.ipos));
     if (al1) J.cu = reinterpret_cast<int32_t *>(const_cast<uint32_t *>(J.iuv));
     if (al2) J.cn = reinterpret_cast<int32_t *>(const_cast<uint32_t *>(J.inrm));
+    if (J.has_mat) J.fmat = all_kept ? J.imat : J.fmat_s;                   // (no face dropped: the stored faces' ids ARE the caller's array)
   }
 }
 

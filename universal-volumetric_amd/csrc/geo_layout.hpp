@@ -22,7 +22,7 @@ __global__ void __launch_bounds__(64) k_layout(GeoJob *jobs) {
   b0 = o;
   a[o++] = 'D'; a[o++] = 'R'; a[o++] = 'A'; a[o++] = 'C'; a[o++] = 'O'; a[o++] = 2; a[o++] = 2; a[o++] = 1; a[o++] = 1; a[o++] = 0; a[o++] = 0;
   a[o++] = 2;
-  o += g_put_varint(a + o, J.nverts); o += g_put_varint(a + o, J.nf); a[o++] = (uint8_t)J.nad;
+  o += g_put_varint(a + o, J.nverts); o += g_put_varint(a + o, J.nf); a[o++] = (uint8_t)(J.nad + J.has_mat);
   o += g_put_varint(a + o, (uint32_t)J.nsym); o += g_put_varint(a + o, (uint32_t)J.nsplit);
   o += g_put_varint(a + o, (uint32_t)J.nev);
   { int last = 0;
@@ -32,6 +32,7 @@ __global__ void __launch_bounds__(64) k_layout(GeoJob *jobs) {
   add_piece(J, a + b0, o - b0, total);
   add_piece(J, J.rb[0].buf + J.rb[0].off, J.rb[0].len, total);
   for (int i = 0; i < J.nad; i++) add_piece(J, J.rb[1 + i].buf + J.rb[1 + i].off, J.rb[1 + i].len, total);
+  if (J.has_mat) add_piece(J, J.rb[GEO_RB_MAT].buf + J.rb[GEO_RB_MAT].off, J.rb[GEO_RB_MAT].len, total);      // attribute data nad: the material's seam stream
   for (int i = 0; i < 6; i++) {
     b0 = o; o += g_put_varint(a + o, J.ctx_n[i]); add_piece(J, a + b0, o - b0, total);
     if (J.ctx_n[i] > 0) add_rans(J, i, total);
@@ -39,15 +40,17 @@ __global__ void __launch_bounds__(64) k_layout(GeoJob *jobs) {
   // attribute decoder headers
   b0 = o;
   const int dec_type[2] = { J.interior_seams[0] ? 1 : 0, J.interior_seams[1] ? 1 : 0 };
-  a[o++] = (uint8_t)(1 + J.nad);
+  a[o++] = (uint8_t)(1 + J.nad + J.has_mat);
   a[o++] = 0xff; a[o++] = 0; a[o++] = 0;
   for (int i = 0; i < J.nad; i++) { a[o++] = (uint8_t)i; a[o++] = (uint8_t)dec_type[i]; a[o++] = 0; }
+  if (J.has_mat) { a[o++] = (uint8_t)J.nad; a[o++] = 0; a[o++] = 0; }       // material: a vertex attribute on the base table, traversal 0
   a[o++] = 1; a[o++] = 0; a[o++] = 9; a[o++] = 3; a[o++] = 0; a[o++] = 0; a[o++] = 2;
   for (int i = 0; i < J.nad; i++) {
     a[o++] = 1;
     if (J.att_kind[i] == 0) { a[o++] = 3; a[o++] = 9; a[o++] = 2; a[o++] = 0; a[o++] = (uint8_t)(1 + i); a[o++] = 2; }
     else { a[o++] = 1; a[o++] = 9; a[o++] = 3; a[o++] = 0; a[o++] = (uint8_t)(1 + i); a[o++] = 3; }
   }
+  if (J.has_mat) { a[o++] = 1; a[o++] = 4; a[o++] = 2; a[o++] = 1; a[o++] = 0; a[o++] = (uint8_t)(1 + J.nad); a[o++] = 1; }      // GENERIC, UINT8, 1 component, not normalised; INTEGER sequential encoder
   // position values
   a[o++] = 1; a[o++] = 1; a[o++] = 1;
   add_piece(J, a + b0, o - b0, total);
@@ -76,6 +79,12 @@ __global__ void __launch_bounds__(64) k_layout(GeoJob *jobs) {
       add_piece(J, J.rb[4].buf + J.rb[4].off, J.rb[4].len, total);
       b0 = o; a[o++] = (uint8_t)J.qn;
     }
+  }
+  if (J.has_mat) {                                                        // parallelogram, wrap, compressed; RAW symbols; the wrap transform's bounds
+    a[o++] = 1; a[o++] = 1; a[o++] = 1;
+    add_piece(J, a + b0, o - b0, total);
+    add_rans(J, GEO_RS_MAT, total);
+    b0 = o; put_i32(a, o, (int32_t)J.mat_lo); put_i32(a, o, (int32_t)J.mat_hi);
   }
   add_piece(J, a + b0, o - b0, total);
   J.out_len = total;

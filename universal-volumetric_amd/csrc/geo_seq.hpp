@@ -122,5 +122,11 @@ __global__ void __launch_bounds__(64) k_stream_setup(GeoJob *jobs) {
     uint32_t ne = J.interior_seams[i] ? J.ne[1 + i] : J.ne[0];
     if (J.att_kind[i] == 0) { J.rs[7].n = 2 * ne; J.ne_uv = ne; } else { J.rs[8].n = 2 * ne; J.ne_nrm = ne; }
   }
+  // material attribute: one symbol per base-table entry; its seam stream is n_elig zero bits (a vertex attribute has no seams)
+  J.rs[GEO_RS_MAT].n = 0;
+  if (J.has_mat) {
+    if (J.mat_seam) { J.status = GEO_E_MAT_SEAM; return; }
+    J.rs[GEO_RS_MAT].n = J.ne[0]; J.rb[GEO_RB_MAT].n = J.n_elig; J.rb[GEO_RB_MAT].zeros = J.n_elig;
+  }
 }
 

@@ -56,6 +56,7 @@ struct GeoDecJob {
   uint8_t *uvgeo;                // GDUvGeo per tex-coord entry
   // outputs (device): position / uv / normal values and per-corner entry indices
   float *o_val[3]; uint32_t *o_idx[3]; uint32_t o_n[3]; int32_t o_dec[3];
+  uint8_t *o_mat; int32_t o_has_mat;      // material id per face (the face order of o_idx), when the file carries a GENERIC uint8 1-component vertex attribute
 };
 
 // ---- byte reader (one lane) ----
@@ -989,6 +990,21 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_finish(GeoDecJob *jobs, Geo
   } else for (int k = 0; k < A.ncomp; k++) o[(size_t)i * A.ncomp + k] = (float)A.vals[(size_t)i * A.ncomp + k];
 }
 
+// Material ids (thread per face): the value of the entry of the face's first corner, for the first decoder that holds a GENERIC (4) UINT8 (2)
+// one-component attribute on the base table (a vertex attribute, dec_type 0) of an edgebreaker file - what stock draco_encoder writes for
+// `usemtl` lines while no two materials meet at a vertex.  A generic attribute of another shape decodes as before and reports no material.
+__global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_facemat(GeoDecJob *jobs, GeoJob *gj) {
+  GeoDecJob &J = jobs[blockIdx.y]; const GeoJob &G = gj[blockIdx.y];
+  if (J.status != 0 || J.method != 1) return;
+  int d = -1;
+  for (int k = 0; k < J.ndec; k++) { const GDAtt &A = J.att[k]; if (A.att_type == 4 && A.data_type == 2 && A.ncomp == 1 && A.dec_type == 0 && A.table == 0 && A.seq_type == 1) { d = k; break; } }
+  if (d < 0) return;
+  const uint32_t f = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (f == 0) J.o_has_mat = 1;
+  if (f >= (uint32_t)J.nf) return;
+  J.o_mat[f] = (uint8_t)J.att[d].vals[G.v2d[0][J.c2v[3 * (size_t)f]]];
+}
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -1082,11 +1098,15 @@ static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool f
   return P.total;
 }
 
-static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev);
-int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool outputs_on_device) {
-  return geo_decode_batch_impl(ctx, files, lens, n, out, status, false, outputs_on_device);
+static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev,
+                                 uint8_t *const *fmat = nullptr, int *has_mat = nullptr);
+int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool outputs_on_device,
+                     uint8_t *const *face_material, int *has_material) {
+  return geo_decode_batch_impl(ctx, files, lens, n, out, status, false, outputs_on_device, face_material, has_material);
 }
-static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev) {
+static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev,
+                                 uint8_t *const *fmat, int *has_mat) {
+  const bool want_mat = fmat != nullptr || has_mat != nullptr;
   GeoDecState *T = ctx->geodec;
   if (n <= 0) return UVOL_OK;
   T->hjobs.assign((size_t)n, GeoDecJob{}); T->hg.assign((size_t)n, GeoJob{});
@@ -1104,7 +1124,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     foff[i] = ftot; ftot += a256(lens[i] + 16);
     GeoJob gtmp{}; const size_t w = gdec_carve(J, gtmp, nullptr, r8, full, T->plan);
     woff[i] = wtot; wtot += a256(w);
-    { const size_t nc = 3 * (size_t)nf; ooff[i] = otot; otot += 3 * (a256(4 * 3 * nc) + a256(4 * nc)); }
+    { const size_t nc = 3 * (size_t)nf; ooff[i] = otot; otot += 3 * (a256(4 * 3 * nc) + a256(4 * nc)) + (want_mat ? a256(nf) : 0); }
   }
   int rc;
   if ((rc = uvol_ensure(ctx, T->files, ftot + 64))) return rc;
@@ -1122,6 +1142,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     const size_t nc = 3 * (size_t)J.nf;
     uint8_t *ob = (uint8_t *)T->outs.p + ooff[i]; size_t oo = 0;
     for (int k = 0; k < 3; k++) { J.o_val[k] = (float *)(ob + oo); oo += a256(4 * 3 * nc); J.o_idx[k] = (uint32_t *)(ob + oo); oo += a256(4 * nc); }
+    J.o_mat = want_mat ? ob + oo : nullptr; J.o_has_mat = 0;
   }
   { const int rcu = uvol_upload_staged(ctx, (uint8_t *)T->files.p, ups); if (rcu != UVOL_OK) return rcu; }
   UVOL_HIP_CHECK(ctx, hipMemcpyAsync(T->jobs.p, T->hjobs.data(), sizeof(GeoDecJob) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -1173,7 +1194,8 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GLAUNCH(k_gdec_normals, dim3(bc, N, GD_MAXDEC), dim3(UVOL_BLOCK), 0, dj, gj);
     GLAUNCH(k_gdec_uvgeo, dim3(bc, N, GD_MAXDEC), dim3(UVOL_BLOCK), 0, dj, gj);
     GLAUNCH(k_gdec_pred, dim3(N, GD_MAXDEC), dim3(64), 0, dj, gj, 1); }
-  { uvol_ctx::Scope sc(ctx, "geodec.k8_finish", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj); }
+  { uvol_ctx::Scope sc(ctx, "geodec.k8_finish", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj);
+    if (want_mat) GLAUNCH(k_gdec_facemat, dim3(uvol_blocks(max_nf), N), dim3(UVOL_BLOCK), 0, dj, gj); }
   UVOL_HIP_CHECK(ctx, hipGetLastError());
   UVOL_HIP_CHECK(ctx, hipMemcpyAsync(T->hjobs.data(), dj, sizeof(GeoDecJob) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1185,11 +1207,17 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
   std::vector<UvolDnItem> dns; if (!out_dev) dns.reserve((size_t)n * 6);      // host outputs: ONE staged download for the whole call (uvol_download_staged)
   for (int i = 0; i < n; i++) {
     const GeoDecJob &J = T->hjobs[i]; uvol_decoded_mesh &M = out[i];
+    if (has_mat) has_mat[i] = 0;
     if (!full && J.status == GD_E_WS_OVERFLOW) { retry.push_back(i); if (status) status[i] = UVOL_OK; continue; }      // decoded again below, alone, with worst-case sizes
     const int st = J.status == 0 ? UVOL_OK : UVOL_E_ENCODE;
     if (status) status[i] = st;
     if (st != UVOL_OK) { ctx->set_error("frame %d: corrupt or unsupported .drc (device status %d)", i, J.status); worst = st; continue; }
     M.n_faces = (uint32_t)J.nf;
+    if (has_mat) has_mat[i] = J.o_has_mat ? 1 : 0;
+    if (J.o_has_mat && fmat && fmat[i]) {
+      if (out_dev) UVOL_HIP_CHECK(ctx, hipMemcpyAsync(fmat[i], J.o_mat, (size_t)J.nf, hipMemcpyDeviceToDevice, ctx->stream));
+      else dns.push_back(UvolDnItem{ J.o_mat, fmat[i], (size_t)J.nf });
+    }
     float *vals[3] = { M.pos, M.uv, M.nrm }; uint32_t *idx[3] = { M.idx_pos, M.idx_uv, M.idx_nrm }; uint32_t *cnt[3] = { &M.n_pos, &M.n_uv, &M.n_nrm };
     const int comps[3] = { 3, 2, 3 };
     for (int k = 0; k < 3; k++) {
@@ -1209,7 +1237,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
   ctx->resolve_profile();
   for (int i : retry) {                                   // frames the compact workspace could not hold (more entries per face than usual)
     int st1 = UVOL_OK;
-    const int rc1 = geo_decode_batch_impl(ctx, files + i, lens + i, 1, out + i, &st1, true, out_dev);
+    const int rc1 = geo_decode_batch_impl(ctx, files + i, lens + i, 1, out + i, &st1, true, out_dev, fmat ? fmat + i : nullptr, has_mat ? has_mat + i : nullptr);
     if (rc1 != UVOL_OK) return rc1;
     if (status) status[i] = st1;
     if (st1 != UVOL_OK) worst = st1;

@@ -13,8 +13,10 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
-#define GEO_NSTREAM 9     // rANS streams: 6 valence contexts, position, uv, normal
-#define GEO_NRABS 5       // rabs streams: start faces, seam uv, seam normal, uv orientations, normal flips
+#define GEO_NSTREAM 10    // rANS streams: 6 valence contexts, position, uv, normal, material (empty for a frame without materials)
+#define GEO_NRABS 6       // rabs streams: start faces, seam uv, seam normal, uv orientations, normal flips, seam material (all zero bits; unused without materials)
+#define GEO_RS_MAT 9      // the material attribute's symbol stream
+#define GEO_RB_MAT 5      // ... and its seam stream
 #define GEO_MAXPIECES 64
 
 struct RansStream {
@@ -42,8 +44,10 @@ struct GeoJob {
   // ---- inputs (device pointers) ----
   const float *pos, *uv, *nrm;
   const uint32_t *ipos, *iuv, *inrm;
+  const uint8_t *imat;          // one material id per INPUT face, or nullptr: the frame has no material attribute
   uint32_t n_pos, n_uv, n_nrm, nf_in;
-  int32_t has_uv, has_nrm, nad;
+  int32_t has_uv, has_nrm, nad;  // nad: the attribute-data slots with seams of their own (uv, normal); the file's count is nad + has_mat
+  int32_t has_mat;
   int32_t qp, qt, qn;
   // ---- state ----
   int32_t status;
@@ -113,6 +117,10 @@ struct GeoJob {
   uint16_t *qpos, *quv, *qnrm;         // quantised values BY VALUE ID (k_quant_ids): 4 x u16 per position (one 8-byte gather), 2 x u16 per uv / octahedral normal
   long long *fnorm;                    // per stored face: the un-normalised face normal (p1 - p0) x (p2 - p0) of its quantised positions (k_face_normals)
   uint32_t *sym_pos, *sym_uv, *sym_nrm;
+  // material attribute (GENERIC uint8, one value per base-table vertex): ids per stored face (the caller's array where no face is
+  // dropped or moved, else fmat_s), per vertex id, their range (the wrap transform's bounds) and 'two ids meet at a vertex'
+  uint8_t *fmat_s; const uint8_t *fmat; uint8_t *vmat; uint32_t *sym_mat;
+  uint32_t mat_lo, mat_hi, mat_seam;      // (whoever adds to this record on behalf of materials: GEO_JOB_MAT_BYTES below counts these fields)
   uint8_t *has_ori, *ori_val, *ori_c, *ori_bits, *flips;
   RansStream rs[GEO_NSTREAM];
   RabsStream rb[GEO_NRABS];
@@ -125,11 +133,15 @@ struct GeoJob {
   uint8_t *out_pack; uint64_t out_pack_off;     // packed output area of the batch + this frame's offset in it (k_out_offsets)
 };
 
+// bytes the material attribute added to the job record: two stream descriptors, six pointers (imat, fmat_s, fmat, vmat, sym_mat + the
+// alignment of has_mat), mat_lo / mat_hi; tests/test_hipemu_material.py pins uvol_mesh_workspace, which leaves them out, to its earlier values
+#define GEO_JOB_MAT_BYTES (sizeof(RansStream) + sizeof(RabsStream) + 6 * sizeof(void *) + 2 * sizeof(uint32_t))
 #define GEO_INV (-1)
 // device status codes the host reacts to: the compact workspace / the packed output area was too small for this frame
 // (geo_encode_batch re-encodes such a frame alone with worst-case sizes)
 #define GEO_E_WS_OVERFLOW (-50)
 #define GEO_E_SLAB_FULL (-51)
+#define GEO_E_MAT_SEAM (-53)           // two material ids meet at a shared vertex (an interior material seam): the frame is refused, not retried
 #define GEO_E_DD_OVERFLOW (-52)        // a hash bin of the partitioned dedup holds more distinct values than its LDS table: retried with the hash-table dedup
 // corner codes for the serial walkers: 4 * face + k, so that face = code >> 2 and records are indexed without a division
 __device__ __forceinline__ int code_of_corner(int c) { return c < 0 ? -1 : (((c / 3) << 2) | (c % 3)); }

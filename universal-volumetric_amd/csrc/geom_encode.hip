@@ -68,6 +68,7 @@ struct GeoLane {
   // the group in flight (submitted, not completed): its slice of the caller's arrays (the pointer arrays are copied: an enqueued call's arrays are gone by then)
   bool busy = false, on_device = false, full = false;
   std::vector<uvol_mesh> meshes; std::vector<uint8_t *> outp; std::vector<size_t> caps;
+  std::vector<const uint8_t *> mats; int frame0 = 0;      // material ids per frame (nullptr: none; empty: no frame has any); index of the group's first frame in its call
   size_t *out_lens = nullptr; int *status = nullptr; int n = 0, n_conc = 0;
   // GPU-resident form (uvol_encode_mesh_batch_dev_out): the packed output area is the CALLER's device buffer and the payload is not copied out
   uint8_t *ext_out = nullptr; size_t ext_cap = 0; size_t *ext_offs = nullptr; hipStream_t producer = nullptr; hipEvent_t ev_prod = nullptr;
@@ -217,7 +218,9 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
   for (int t = 0; t < 3; t++) CARVE(J.t_vvis[t], uint8_t, ecap / 8 + 64, PH_PINNED, PH_PINNED);
   for (int s = 0; s < GEO_NSTREAM; s++) {
     const int q = s == 6 ? J.qp : (s == 7 ? J.qt : J.qn);
-    J.rs[s].alpha_cap = s < 6 ? 8 : (1u << (q + 1)) + 8;
+    // (material ids: wrap corrections over a range of at most 256 values, symbols below 256; a frame without materials has no such stream)
+    if (s == GEO_RS_MAT) { J.rs[s].alpha_cap = J.has_mat ? 512 + 8 : 0; if (!J.has_mat) continue; }
+    else J.rs[s].alpha_cap = s < 6 ? 8 : (1u << (q + 1)) + 8;
     CARVE(J.rs[s].freq, uint32_t, J.rs[s].alpha_cap, PH_PINNED, PH_PINNED);
   }
   // ---- scan scratch (tiny, kept for the whole batch) ----
@@ -226,6 +229,11 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
   { const int cl = J.seq ? PH_LAYOUT : PH_FACES;          // the sequential path reads the canonical ids when it quantises the points
     CARVE(J.canon[0], uint32_t, J.n_pos + 1, PH_DEDUP, cl); CARVE(J.canon[1], uint32_t, J.n_uv + 1, PH_DEDUP, cl); CARVE(J.canon[2], uint32_t, J.n_nrm + 1, PH_DEDUP, cl); }
   CARVE(J.keep, uint8_t, nfi + 1, PH_FACES, PH_FACES);
+  // material ids: per stored face where faces are dropped or moved (else the caller's array is read, k_compact_faces), per vertex id, symbols
+  if (J.has_mat) {
+    if (!J.compact) CARVE(J.fmat_s, uint8_t, nfi + 1, PH_FACES, PH_PRED);
+    CARVE(J.vmat, uint8_t, ecap, PH_PRED, PH_PRED); CARVE(J.sym_mat, uint32_t, ecap, PH_PRED, PH_ENT);
+  }
   // the stored corner table (canonical value ids, opposite corners, vertex ids) lives until the predictors: nothing is renumbered
   // (the compact layout has no copies: every frame's ids are its caller's index arrays, or the group is laid out again - geo_submit_impl)
   if (!J.compact) { CARVE(J.cp, int32_t, nc + 3, PH_FACES, PH_PRED); CARVE(J.cu, int32_t, nc + 3, PH_FACES, PH_PRED); CARVE(J.cn, int32_t, nc + 3, PH_FACES, PH_PRED); }
@@ -280,7 +288,9 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
   // ---- K7 ----
   for (int s = 0; s < GEO_NSTREAM; s++) {
     RansStream &S = J.rs[s];
-    const size_t nsym = s < 6 ? nfi : (s == 6 ? 3 * ecap : 2 * ecap);
+    S.syms = nullptr; S.n = 0; S.max_sym = 0; S.head_len = 0; S.pay_len = 0; S.pay_off = 0; S.prec_bits = 12;
+    if (s == GEO_RS_MAT && !J.has_mat) continue;
+    const size_t nsym = s < 6 ? nfi : (s == 6 ? 3 * ecap : (s == GEO_RS_MAT ? ecap : 2 * ecap));
     CARVE(S.probs, uint32_t, S.alpha_cap, PH_HIST, PH_LAYOUT); CARVE(S.cum, uint32_t, S.alpha_cap, PH_HIST, PH_LAYOUT);
     CARVE(S.head, uint8_t, 3 * (size_t)S.alpha_cap + 32, PH_HIST, PH_LAYOUT);
     CARVE(S.tab, uint4, S.alpha_cap, PH_HIST, PH_ENT);
@@ -288,13 +298,13 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
     // counting-sort scratch of k_rans_tables: (precision + 2) counters + one slot per symbol of the alphabet
     const int bl = bitlen(S.alpha_cap), pb = std::min(20, std::max(12, 3 * bl / 2));
     CARVE(S.scratch, uint32_t, ((size_t)1 << pb) + 4 + S.alpha_cap, PH_HIST, PH_HIST);
-    S.syms = nullptr; S.n = 0; S.max_sym = 0; S.head_len = 0; S.pay_len = 0; S.pay_off = 0; S.prec_bits = 12;
   }
   for (int b = 0; b < GEO_NRABS; b++) {
     RabsStream &B = J.rb[b];
-    const size_t nb = b == 0 ? nfi : (b < 3 ? nc : ecap);
-    B.cap = (uint32_t)(nb / 4 + nb / 8 + 256); CARVE(B.buf, uint8_t, B.cap, PH_ENT, PH_LAYOUT);
     B.bits = nullptr; B.n = 0; B.zeros = 0; B.off = 0; B.len = 0;
+    if (b == GEO_RB_MAT && !J.has_mat) { B.cap = 0; continue; }
+    const size_t nb = b == 0 ? nfi : ((b < 3 || b == GEO_RB_MAT) ? nc : ecap);
+    B.cap = (uint32_t)(nb / 4 + nb / 8 + 256); CARVE(B.buf, uint8_t, B.cap, PH_ENT, PH_LAYOUT);
   }
   J.arena_cap = (uint32_t)(20 * nfi + 1024); CARVE(J.arena, uint8_t, J.arena_cap, PH_LAYOUT, PH_LAYOUT);
 #undef CARVE
@@ -316,7 +326,7 @@ const WsPlan &layout_job(GeoJob &J, uint8_t *base, bool full, int fmt0, int fmtT
   ws_collect(J, full, fmt0, fmtT, items);
   auto up = [](uint32_t v, uint32_t q) { return (uint64_t)((v + (uint64_t)q - 1) / q) * q; };
   const uint64_t flags = (uint64_t)J.qp | ((uint64_t)J.qt << 8) | ((uint64_t)J.qn << 16) | ((uint64_t)full << 24) | ((uint64_t)(J.relabel != 0) << 26) |
-                         ((uint64_t)(J.seq != 0) << 27) | ((uint64_t)(J.late_join != 0) << 28) | ((uint64_t)fmt0 << 29) | ((uint64_t)fmtT << 31) | ((uint64_t)(J.compact != 0) << 33);      // everything ws_collect's sizes AND lifetimes depend on
+                         ((uint64_t)(J.seq != 0) << 27) | ((uint64_t)(J.late_join != 0) << 28) | ((uint64_t)fmt0 << 29) | ((uint64_t)fmtT << 31) | ((uint64_t)(J.compact != 0) << 33) | ((uint64_t)(J.has_mat != 0) << 34);      // everything ws_collect's sizes AND lifetimes depend on
   std::vector<uint64_t> key = { up(J.nf_in, 2048), up(J.n_pos, 1024), up(J.n_uv, 1024), up(J.n_nrm, 1024), flags, items.size(), 0 };
   auto it = C.plans.find(key);
   if (it == C.plans.end()) {
@@ -463,6 +473,8 @@ int geo_run_traversals(uvol_ctx *ctx, GeoJob *dj, int n, uint32_t max_nfi, uint3
 }
 
 // device workspace one frame of these dimensions holds while it is in flight (compact layout + its share of the packed output area)
+// a frame with materials adds one section of a few bytes per component and its (all-zero) seam stream
+extern "C" size_t uvol_mesh_bound_mat(const uvol_mesh *m) { return m ? uvol_mesh_bound(m) + 4096 + 8 * (size_t)m->n_faces : 0; }
 extern "C" size_t uvol_mesh_workspace(const uvol_ctx *ctx, const uvol_mesh *m) {
   if (!ctx || !m || !m->n_faces) return 0;
   GeoJob J{}; J.compact = 1;        // (a clean frame of a large batch: the compact layout; a group with unclean frames holds 36 bytes per face more)
@@ -475,7 +487,9 @@ extern "C" size_t uvol_mesh_workspace(const uvol_ctx *ctx, const uvol_mesh *m) {
   WsPlanCache P1; std::vector<WsItem> items1; GeoJob J1 = J; J1.compact = 0;
   const int fmt1 = fmt ? 1 : 0;
   const size_t small = layout_job(J1, nullptr, false, fmt1, fmt1, P1, items1).total;
-  return std::max(big, small) + 32768 + 8 * (size_t)m->n_faces + sizeof(GeoJob);
+  // (the job record is counted without the descriptors of the material attribute's two streams and its fields: the value of a frame without
+  // materials is what it was before they existed, and the entry point has no material argument)
+  return std::max(big, small) + 32768 + 8 * (size_t)m->n_faces + (sizeof(GeoJob) - GEO_JOB_MAT_BYTES);
 }
 // stages of a batch with sequential connectivity, between k_minmax and the layout (all parallel; see k_sq_*)
 static int geo_encode_sequential(uvol_ctx *ctx, GeoJob *dj, int n, bool full, uint32_t max_nfi, uint32_t max_vals, uint32_t max_ecap, uint64_t algo_in) {
@@ -527,7 +541,7 @@ static int geo_encode_sequential(uvol_ctx *ctx, GeoJob *dj, int n, bool full, ui
   return UVOL_OK;
 }
 static int geo_submit(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n, int n_conc, bool on_device,
-                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool full, GeoUp *pre = nullptr);
+                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool full, GeoUp *pre = nullptr, const uint8_t *const *mats = nullptr);
 static int geo_complete(uvol_ctx *ctx, GeoLane &L);
 
 // First half of a group of frames on lane L: lays out the workspaces, uploads host inputs, enqueues every kernel of the group and the
@@ -536,6 +550,8 @@ static int geo_complete(uvol_ctx *ctx, GeoLane &L);
 // call (what is on the chip together decides the kernel forms, not this group's share).
 static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n, int n_conc, bool on_device, const size_t *caps, bool full) {
   GeoState *G = ctx->geo;
+  const uint8_t *const *mats = L.mats.empty() ? nullptr : L.mats.data();
+  bool any_mat = false; for (int i = 0; mats && i < n; i++) any_mat = any_mat || mats[i] != nullptr;
   const auto t_enter = std::chrono::steady_clock::now();
   auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
   const uvol_params &prm = ctx->prm;
@@ -598,12 +614,13 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     J.n_pos = m.n_pos; J.nf_in = m.n_faces; J.relabel = seq ? 0 : geo_relabel_mode(); J.seq = seq ? 1 : 0; J.late_join = late_join ? 1 : 0;
     J.has_uv = (m.uv && m.idx_uv && m.n_uv) ? 1 : 0; J.has_nrm = (m.nrm && m.idx_nrm && m.n_nrm) ? 1 : 0;
     J.n_uv = J.has_uv ? m.n_uv : 0; J.n_nrm = J.has_nrm ? m.n_nrm : 0;
+    J.has_mat = (mats && mats[i]) ? 1 : 0; J.mat_lo = 0xffffffffu; J.mat_hi = 0;
     J.nad = J.has_uv + J.has_nrm; J.qp = prm.q_position_attr; J.qt = prm.q_texture_attr; J.qn = prm.q_normal_attr;
     { int k = 0; if (J.has_uv) J.att_kind[k++] = 0; if (J.has_nrm) J.att_kind[k++] = 1; for (; k < 2; k++) J.att_kind[k] = -1; }
     const WsPlan &wp = layout_job(J, nullptr, full, fmt0, fmtT, G->plan, G->items);
     ws_off[i] = ws_total; ws_total += wp.total; zero_sz[i] = wp.zero;
     const size_t in_sz = ((size_t)m.n_pos * 12 + 255) / 256 * 256 + ((size_t)J.n_uv * 8 + 255) / 256 * 256 + ((size_t)J.n_nrm * 12 + 255) / 256 * 256 +
-                         (size_t)(1 + J.has_uv + J.has_nrm) * (((size_t)m.n_faces * 12 + 255) / 256 * 256);
+                         (size_t)(1 + J.has_uv + J.has_nrm) * (((size_t)m.n_faces * 12 + 255) / 256 * 256) + (J.has_mat ? ((size_t)m.n_faces + 255) / 256 * 256 : 0);
     in_off[i] = in_total; in_total += (on_device || pre_up) ? 0 : in_sz;
     // the frames' streams are packed back to back (k_out_offsets), so the batch's output area is sized for typical streams
     // (8 bytes per face; the defaults give 1.3), not for the sum of the callers' capacities; GEO_E_SLAB_FULL -> retried alone
@@ -635,7 +652,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     if (base_shared) { J.rec[1] = J.rec[0]; J.base_hi = 1; }      // the traversals' base table is the walk's record table (flag bit 127)
     J.ws_base = base; J.ws_zero = zero_sz[i];          // cleared by ONE k_job_clear launch for the whole batch (was 2 memsets per frame)
     if (L.ext_out) { J.out_pack = L.ext_out; J.slab_cap = L.ext_cap; } else { J.out_pack = (uint8_t *)L.outs.p; J.slab_cap = out_total; }
-    if (on_device) { J.pos = m.pos; J.uv = J.has_uv ? m.uv : nullptr; J.nrm = J.has_nrm ? m.nrm : nullptr; J.ipos = m.idx_pos; J.iuv = J.has_uv ? m.idx_uv : nullptr; J.inrm = J.has_nrm ? m.idx_nrm : nullptr; }
+    if (on_device) { J.pos = m.pos; J.uv = J.has_uv ? m.uv : nullptr; J.nrm = J.has_nrm ? m.nrm : nullptr; J.ipos = m.idx_pos; J.iuv = J.has_uv ? m.idx_uv : nullptr; J.inrm = J.has_nrm ? m.idx_nrm : nullptr; J.imat = J.has_mat ? mats[i] : nullptr; }
     else if (pre_up) {                                       // already on their way: the group's uplink slot (geo_encode_batch_begin)
       const uint8_t *sb = (const uint8_t *)L.up.slot->buf.p; const size_t *o6 = &L.up.off[(size_t)i * 6];
       J.pos = (const float *)(sb + o6[0]); J.uv = J.has_uv ? (const float *)(sb + o6[1]) : nullptr; J.nrm = J.has_nrm ? (const float *)(sb + o6[2]) : nullptr;
@@ -651,12 +668,13 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
       J.ipos = (const uint32_t *)up(m.idx_pos, (size_t)m.n_faces * 12);
       J.iuv = J.has_uv ? (const uint32_t *)up(m.idx_uv, (size_t)m.n_faces * 12) : nullptr;
       J.inrm = J.has_nrm ? (const uint32_t *)up(m.idx_nrm, (size_t)m.n_faces * 12) : nullptr;
+      J.imat = J.has_mat ? (const uint8_t *)up(mats[i], (size_t)m.n_faces) : nullptr;
     }
     for (int k = 0; k < 3; k++) { J.pos_min_u[k] = 0xffffffffu; J.pos_max_u[k] = 0; }
     for (int k = 0; k < 2; k++) { J.uv_min_u[k] = 0xffffffffu; J.uv_max_u[k] = 0; J.wrap_lo[k] = 0x7fffffff; J.wrap_hi[k] = -0x7fffffff - 1; }
     // stream wiring
     for (int s = 0; s < 6; s++) J.rs[s].syms = J.ctx_sym[s];
-    J.rs[6].syms = J.sym_pos; J.rs[7].syms = J.sym_uv; J.rs[8].syms = J.sym_nrm;
+    J.rs[6].syms = J.sym_pos; J.rs[7].syms = J.sym_uv; J.rs[8].syms = J.sym_nrm; J.rs[GEO_RS_MAT].syms = J.sym_mat;      // (the material's seam stream, rb[GEO_RB_MAT], is zero bits: no array)
     J.rb[0].bits = J.start_bits; J.rb[1].bits = J.seam_bits[0]; J.rb[2].bits = J.seam_bits[1]; J.rb[3].bits = J.ori_bits; J.rb[4].bits = J.flips;
     // rabs slot 1/2 follow the attribute-data slot; slot 3 = uv orientations, slot 4 = normal flips
   }
@@ -879,6 +897,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
   { uvol_ctx::Scope sc(ctx, "geo.k5b_v2d", 0); LAUNCH(k_v2d, dim3(be, N, 3), dim3(UVOL_BLOCK), dj, fmtT); }      // (own scope: geo.k5_traverse is exactly the traversal kernel, as rocprof lists it)
   {
     uvol_ctx::Scope sc(ctx, "geo.k6_predict", 0);
+    if (any_mat) { LAUNCH(k_mat_vert, dim3(bc, N), dim3(UVOL_BLOCK), dj, 0); LAUNCH(k_mat_vert, dim3(bc, N), dim3(UVOL_BLOCK), dj, 1); }      // ids per vertex, then the seam test (k_stream_setup refuses the frame)
     LAUNCH(k_stream_setup, dim3(N), dim3(64), dj);
     LAUNCH(k_pred_pos, dim3(be, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_pred_uv, dim3(be, N), dim3(UVOL_BLOCK), dj);
@@ -888,12 +907,15 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     LAUNCH(k_ori_bits, dim3(be, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_face_normals, dim3(bf, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_pred_nrm, dim3(be, N), dim3(UVOL_BLOCK), dj);
+    if (any_mat) LAUNCH(k_pred_mat, dim3(be, N), dim3(UVOL_BLOCK), dj);
   }
   if (late_join) UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, L.ev_val, 0));
   {
     uvol_ctx::Scope sc0(ctx, "geo.k7_hist_tables", 0);
-    LAUNCH(k_hist, dim3(uvol_blocks((size_t)9 * max_nfi, 16 * UVOL_BLOCK), GEO_NSTREAM, N), dim3(UVOL_BLOCK), dj);
-    LAUNCH(k_rans_tables, dim3(GEO_NSTREAM, N), dim3(64), dj);
+    // (a group without materials does not launch the material stream's - empty - row of workgroups)
+    const unsigned NS = any_mat ? GEO_NSTREAM : GEO_NSTREAM - 1;
+    LAUNCH(k_hist, dim3(uvol_blocks((size_t)9 * max_nfi, 16 * UVOL_BLOCK), NS, N), dim3(UVOL_BLOCK), dj);
+    LAUNCH(k_rans_tables, dim3(NS, N), dim3(64), dj);
   }
   {
     uvol_ctx::Scope sc(ctx, "geo.k7_entropy_encode", 0);
@@ -903,15 +925,19 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     // UVOL_ENTROPY_WAVE=1 / 0 (tests / diagnostic) forces one form.
     static const int ent_env = [] { const char *e = getenv("UVOL_ENTROPY_WAVE"); return !e ? -1 : (*e == '1' ? 1 : 0); }();
     static const int ent_w_env = [] { const char *e = getenv("UVOL_ENTROPY_W"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > 64 ? 64 : v); }();   // lanes per wave of the lane form (implies it)
-    const bool ent_wave = ent_env >= 0 ? ent_env == 1 : (ent_w_env == 0 && (size_t)(GEO_NSTREAM + GEO_NRABS) * NC <= (size_t)20 * G->num_cu);
+    const size_t per_frame = any_mat ? GEO_NSTREAM + GEO_NRABS : GEO_NSTREAM + GEO_NRABS - 2;      // streams that do any work per frame
+    const bool ent_wave = ent_env >= 0 ? ent_env == 1 : (ent_w_env == 0 && per_frame * NC <= (size_t)20 * G->num_cu);
     if (ent_wave) LAUNCH(k_entropy_encode, dim3(N, GEO_NSTREAM + GEO_NRABS), dim3(64), dj, uvol_debug() ? 1 : 0);      // frame index fastest: the long streams of the frames spread over the four SIMDs of a CU (geom_decode.hip: k_gdec_rans)
     else {
       // lanes per wave: five streams of a frame are long (three attribute symbol streams, two seam-bit streams; ~300 k steps) and a
       // wave runs as long as its longest lane, so the launch should put at most ONE long wave on a SIMD (1024 of them): waves that
       // share a SIMD share its issue slots (2160 frames: 172 / 105 / 60 / 64 / 55 / 52 ms with 1 / 2 / 4 / 8 / 16 / 32 lanes per wave)
+      // (a frame with materials has two more streams - its material symbols and its all-zero seam stream, neither of which fetches a table
+      // entry or a flag per step -; counting them as long ones doubles W at 2560 frames and measured slower: 109.5 against 72.3 ms)
       unsigned W = 4; while (W < 64 && 5u * NC > 512u * W) W *= 2;
       if (ent_w_env) W = (unsigned)ent_w_env;
-      LAUNCH(k_rans_recip, dim3(uvol_blocks(((size_t)2 << std::max(prm.q_position_attr, std::max(prm.q_texture_attr, prm.q_normal_attr))) + 8), GEO_NSTREAM, N), dim3(UVOL_BLOCK), dj);
+      const size_t max_alpha = std::max<size_t>(((size_t)2 << std::max(prm.q_position_attr, std::max(prm.q_texture_attr, prm.q_normal_attr))) + 8, any_mat ? 512 + 8 : 0);
+      LAUNCH(k_rans_recip, dim3(uvol_blocks(max_alpha), any_mat ? GEO_NSTREAM : GEO_NSTREAM - 1, N), dim3(UVOL_BLOCK), dj);
       LAUNCH_SM(k_entropy_simt, dim3((N + W - 1) / W, GEO_NSTREAM + GEO_NRABS), dim3(64), (size_t)W * SB_STRIDE * 4, dj, n, (int)W);
     }
   }
@@ -973,13 +999,15 @@ static int geo_complete_impl(uvol_ctx *ctx, GeoLane &L) {
     if (L.ext_offs) L.ext_offs[i] = (size_t)J.out_pack_off;
     if (st == UVOL_OK) { }
     else if (!full && (J.status == GEO_E_WS_OVERFLOW || J.status == GEO_E_SLAB_FULL || J.status == GEO_E_DD_OVERFLOW)) { retry.push_back(i); st = UVOL_OK; }
-    else { ctx->set_error("mesh %d: encode failed (device status %d)", i, J.status); worst = st; }
+    else if (J.status == GEO_E_MAT_SEAM) { st = UVOL_E_UNSUPPORTED; ctx->set_error("mesh %d: two materials meet at a shared vertex (interior material seam): not supported, encode the frame without materials", L.frame0 + i); worst = st; }
+    else { ctx->set_error("mesh %d: encode failed (device status %d)", L.frame0 + i, J.status); worst = st; }
     if (status) status[i] = st;
   }
   // frames the compact workspace (or the packed output area) could not hold: once more, alone, with worst-case sizes
   if (!retry.empty()) {
     // the lane's own record of the group is replaced by the one-frame retries: keep what is still needed
     const std::vector<uvol_mesh> rm(L.meshes); const std::vector<uint8_t *> ro(L.outp); const std::vector<size_t> rcap(L.caps);
+    const std::vector<const uint8_t *> rmat(L.mats); const int frame0 = L.frame0;
     // GPU-resident form: a retried frame goes behind the frames already packed into the caller's buffer
     uint8_t *const ext0 = L.ext_out; const size_t ext_cap0 = L.ext_cap; size_t *const offs0 = L.ext_offs; size_t tail = 0;
     if (ext0) for (int i = 0; i < n; i++) { const GeoJob &J = L.hjobs[i]; if (J.status == 0) tail = std::max<size_t>(tail, ((size_t)J.out_pack_off + J.out_len + 255) & ~(size_t)255); }
@@ -991,8 +1019,11 @@ static int geo_complete_impl(uvol_ctx *ctx, GeoLane &L) {
         L.ext_out = ext0 + tail; L.ext_cap = ext_cap0 - tail; L.ext_offs = nullptr; L.producer = nullptr;
       }
       size_t cap1 = ext0 ? std::min<size_t>(ext_cap0 - tail, 0xffffffffu) : rcap[i];
-      int rc1 = geo_submit(ctx, L, &rm[i], 1, 1, on_device, &ro[i], &cap1, out_lens + i, &st1, true);
+      const uint8_t *mat1 = rmat.empty() ? nullptr : rmat[i];
+      L.frame0 = frame0 + i;
+      int rc1 = geo_submit(ctx, L, &rm[i], 1, 1, on_device, &ro[i], &cap1, out_lens + i, &st1, true, nullptr, mat1 ? &mat1 : nullptr);
       if (rc1 == UVOL_OK) rc1 = geo_complete(ctx, L);
+      L.frame0 = frame0;
       if (ext0) { L.ext_out = ext0; L.ext_cap = ext_cap0; L.ext_offs = offs0; if (offs0) offs0[i] = tail; if (rc1 == UVOL_OK && st1 == UVOL_OK) tail = (tail + out_lens[i] + 255) & ~(size_t)255; }
       if (rc1 != UVOL_OK) return rc1;
       if (status) status[i] = st1;
@@ -1006,8 +1037,9 @@ static int geo_complete_impl(uvol_ctx *ctx, GeoLane &L) {
 
 // the lane's streams stand in for the context's while one of its groups is submitted / completed (LAUNCH, Scope, uvol_ensure use ctx->stream)
 static int geo_submit(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n, int n_conc, bool on_device,
-                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool full, GeoUp *pre) {
+                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool full, GeoUp *pre, const uint8_t *const *mats) {
   if (pre) L.up = std::move(*pre); else { L.up.slot = nullptr; L.up.off.clear(); }
+  if (mats) L.mats.assign(mats, mats + n); else L.mats.clear();
   L.meshes.assign(meshes, meshes + n); L.outp.assign(outs, outs + n); L.caps.assign(caps, caps + n);
   L.out_lens = out_lens; L.status = status; L.n = n; L.n_conc = n_conc; L.on_device = on_device; L.full = full;
   hipStream_t saved = ctx->stream; ctx->stream = L.stream;
@@ -1058,9 +1090,10 @@ static inline int geo_min_group() { static const int v = [] { const char *e = ge
 // split: cut the call into groups (enqueued calls, whose successor overlaps their tail; blocking calls with HOST inputs, whose groups
 // upload while the groups before them encode); a blocking call on device inputs stays one group.
 int geo_encode_batch_begin(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool on_device,
-                           uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool split) {
+                           uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool split, const uint8_t *const *mats, int frame0) {
   GeoState *G = ctx->geo;
   if (n <= 0) return UVOL_OK;
+  { bool any = false; for (int i = 0; mats && i < n; i++) any = any || mats[i] != nullptr; if (!any) mats = nullptr; }      // (no frame has materials: the call without them)
   // host inputs: four groups at least (a group uploads while the groups before it encode; the first group's upload is the only one nothing hides)
   const int want = std::max(1, std::min(G->lanes_cap, on_device ? geo_lanes_wanted() : std::max(geo_lanes_wanted(), 4)));
   static const int split_env = [] { const char *e = getenv("UVOL_GEO_SPLIT"); return e ? atoi(e) : -1; }();      // tests / diagnostic: 1 / 0 force / forbid the split
@@ -1073,7 +1106,7 @@ int geo_encode_batch_begin(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool o
   // cut like a call on device inputs.  (Round 5 cut every host call into as many groups as the ring has lanes: consecutive enqueued calls then
   // met lane by lane - group g of call c + 1 waited for group g of call c - and the six groups of a call ran their walkers, then their
   // traversals, side by side, bunched: 2333 frames/s geometry alone against 5307 on device inputs, profiles/r06_uplink_forms.json.)
-  bool up_all = !on_device && uvol_uplink_enabled() && split && n >= 1;
+  bool up_all = !on_device && uvol_uplink_enabled() && split && n >= 1 && !mats;      // (host material ids travel with the staged inputs)
   for (int i = 0; i < n && up_all; i++) {
     const uvol_mesh &m = meshes[i];
     if (!m.pos || !m.idx_pos || m.n_pos == 0 || m.n_faces == 0) { up_all = false; break; }                    // (geo_submit reports the invalid frame)
@@ -1122,7 +1155,8 @@ int geo_encode_batch_begin(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool o
     if (!L) { ctx->set_error("geometry lane: stream / event creation failed"); return UVOL_E_HIP; }
     if (split) G->next_lane = (G->next_lane + 1) % want;
     if (L->busy) { const int r = geo_complete(ctx, *L); if (r != UVOL_OK && G->deferred_rc == UVOL_OK) G->deferred_rc = r; }
-    const int rc = geo_submit(ctx, *L, meshes + a, b - a, n, on_device, outs + a, caps + a, out_lens + a, status ? status + a : nullptr, false, ups_pre.empty() ? nullptr : &ups_pre[(size_t)g]);
+    L->frame0 = frame0 + a;
+    const int rc = geo_submit(ctx, *L, meshes + a, b - a, n, on_device, outs + a, caps + a, out_lens + a, status ? status + a : nullptr, false, ups_pre.empty() ? nullptr : &ups_pre[(size_t)g], mats ? mats + a : nullptr);
     if (rc != UVOL_OK) {
       // the slots this call filled and nobody will read: their copies must not outlive the caller's arrays (the call has failed)
       if (!ups_pre.empty() && ctx->uplink) (void)hipStreamSynchronize(ctx->uplink->stream);
@@ -1155,7 +1189,7 @@ int geo_encode_batch_dev_out(uvol_ctx *ctx, const uvol_mesh *meshes, int n, hipS
   GeoLane *L = geo_lane(ctx, 0);
   if (!L) { ctx->set_error("geometry lane: stream / event creation failed"); return UVOL_E_HIP; }
   std::vector<uint8_t *> outs((size_t)n, nullptr); std::vector<size_t> caps((size_t)n, std::min<size_t>(dev_cap, 0xffffffffu));
-  L->ext_out = dev_out; L->ext_cap = dev_cap; L->ext_offs = out_offs; L->producer = producer;
+  L->ext_out = dev_out; L->ext_cap = dev_cap; L->ext_offs = out_offs; L->producer = producer; L->frame0 = 0;
   int rc = geo_submit(ctx, *L, meshes, n, n, true, outs.data(), caps.data(), out_lens, status, false);
   if (rc == UVOL_OK) rc = geo_complete(ctx, *L);
   L->ext_out = nullptr; L->ext_cap = 0; L->ext_offs = nullptr; L->producer = nullptr;
@@ -1164,9 +1198,9 @@ int geo_encode_batch_dev_out(uvol_ctx *ctx, const uvol_mesh *meshes, int n, hipS
 }
 // blocking form: begin + flush
 int geo_encode_batch(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool on_device,
-                     uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
+                     uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, const uint8_t *const *mats, int frame0) {
   ctx->geo->blocking_call = true;
-  const int rc = geo_encode_batch_begin(ctx, meshes, n, on_device, outs, caps, out_lens, status, !on_device);
+  const int rc = geo_encode_batch_begin(ctx, meshes, n, on_device, outs, caps, out_lens, status, !on_device, mats, frame0);
   ctx->geo->blocking_call = false;
   const int rf = geo_flush(ctx);
   return rc != UVOL_OK ? rc : rf;

@@ -18,15 +18,18 @@
 
 #define OBJ_BPT 16                         // bytes per thread
 #define OBJ_TILE (UVOL_BLOCK * OBJ_BPT)    // bytes per workgroup
-enum { OBJ_V = 0, OBJ_VT = 1, OBJ_VN = 2, OBJ_TRI = 3 };
+enum { OBJ_V = 0, OBJ_VT = 1, OBJ_VN = 2, OBJ_TRI = 3, OBJ_MTL = 4, OBJ_NK = 5 };      // OBJ_MTL: `usemtl` lines
 #define OBJ_E_HARD (-60)                   // irregular text: the host parser decides
 #define OBJ_E_BADFACE (-61)                // a face references a missing vertex
 #define OBJ_E_EMPTY (-62)                  // no faces / no positions
 
 struct ObjJob {
   const uint8_t *text; uint32_t len, nblk;
-  uint32_t *bcnt;                          // [4][nblk + 1] per-workgroup counts, then their exclusive scans (+ totals)
-  uint32_t tot[4];
+  uint32_t *bcnt;                          // [OBJ_NK][nblk + 1] per-workgroup counts, then their exclusive scans (+ totals)
+  uint32_t tot[OBJ_NK];
+  // material ids (uvol_parse_obj_batch_dev_mat): pass 2 writes one record per `usemtl` line {file position of the line, triangles ranked before
+  // it}; the host resolves the names to ids (one per record, mid) and k_obj_mat_expand turns the runs into one byte per triangle (fmat)
+  uint2 *mrec; const uint8_t *mid; uint8_t *fmat;
   float *pos, *uv, *nrm; uint32_t *ipos, *iuv, *inrm;
   int32_t status; uint32_t no_uv, no_n;
 };
@@ -39,6 +42,7 @@ __device__ __forceinline__ int obj_kind(const uint8_t *t, uint32_t p, uint32_t l
   if (p + 2 < le && t[p] == 'v' && t[p + 1] == 't' && (t[p + 2] == ' ' || t[p + 2] == '\t')) { q = p + 2; return OBJ_VT; }
   if (p + 2 < le && t[p] == 'v' && t[p + 1] == 'n' && (t[p + 2] == ' ' || t[p + 2] == '\t')) { q = p + 2; return OBJ_VN; }
   if (p + 1 < le && t[p] == 'f' && (t[p + 1] == ' ' || t[p + 1] == '\t')) { q = p + 1; return 3; }
+  if (p + 6 < le && t[p] == 'u' && t[p + 1] == 's' && t[p + 2] == 'e' && t[p + 3] == 'm' && t[p + 4] == 't' && t[p + 5] == 'l' && (t[p + 6] == ' ' || t[p + 6] == '\t')) { q = p + 6; return OBJ_MTL; }
   return -1;
 }
 __device__ __forceinline__ uint32_t obj_line_end(const uint8_t *t, uint32_t p, uint32_t len) { while (p < len && t[p] != '\n') p++; return p; }
@@ -122,7 +126,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_obj_count(ObjJob *jobs) {
   const uint32_t tile0 = blockIdx.x * OBJ_TILE, wend = len - tile0 > OBJ_TILE + OBJ_OVER ? tile0 + OBJ_TILE + OBJ_OVER : len;
   const uint8_t *ts = obj_stage(tg, len, tile0, stage);
   const uint32_t b0 = tile0 + threadIdx.x * OBJ_BPT;
-  uint32_t c[4] = { 0, 0, 0, 0 };
+  uint32_t c[OBJ_NK] = { 0, 0, 0, 0, 0 };
   for (uint32_t i = b0; i < b0 + OBJ_BPT && i < len; i++) {
     if (i != 0 && ts[(int)(i - tile0) - 1] != '\n') continue;
     const uint8_t *t; uint32_t li; const uint32_t le = obj_line_window(ts, tg, i, tile0, wend, len, t, li); uint32_t q;
@@ -130,12 +134,12 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_obj_count(ObjJob *jobs) {
     if (k == 3) { const uint32_t nc = obj_face_corners(t, q, le); c[OBJ_TRI] += nc > 2 ? nc - 2 : 0; }
     else if (k >= 0) c[k]++;
   }
-  __shared__ uint32_t acc[4];
-  if (threadIdx.x < 4) acc[threadIdx.x] = 0;
+  __shared__ uint32_t acc[OBJ_NK];
+  if (threadIdx.x < OBJ_NK) acc[threadIdx.x] = 0;
   __syncthreads();
-  for (int k = 0; k < 4; k++) { uint32_t v = c[k]; for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d); if ((threadIdx.x & 63) == 0 && v) atomicAdd(&acc[k], v); }
+  for (int k = 0; k < OBJ_NK; k++) { uint32_t v = c[k]; for (int d = 32; d >= 1; d >>= 1) v += __shfl_down(v, d); if ((threadIdx.x & 63) == 0 && v) atomicAdd(&acc[k], v); }
   __syncthreads();
-  if (threadIdx.x < 4) J.bcnt[(size_t)threadIdx.x * (J.nblk + 1) + blockIdx.x] = acc[threadIdx.x];
+  if (threadIdx.x < OBJ_NK) J.bcnt[(size_t)threadIdx.x * (J.nblk + 1) + blockIdx.x] = acc[threadIdx.x];
 }
 // exclusive scan of the workgroup counts (one workgroup per frame and kind)
 __global__ void __launch_bounds__(UVOL_BLOCK) k_obj_scan(ObjJob *jobs) {
@@ -170,7 +174,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_obj_parse(ObjJob *jobs) {
   const uint32_t b0 = tile0 + threadIdx.x * OBJ_BPT;
   const bool live = J.status == 0;
   // this thread's lines: counts first (as in pass 1), then an exclusive scan over the workgroup gives the rank of its first line of each kind
-  uint32_t c[4] = { 0, 0, 0, 0 };
+  uint32_t c[OBJ_NK] = { 0, 0, 0, 0, 0 };
   if (live) for (uint32_t i = b0; i < b0 + OBJ_BPT && i < len; i++) {
     if (i != 0 && ts[(int)(i - tile0) - 1] != '\n') continue;
     const uint8_t *t; uint32_t li; const uint32_t le = obj_line_window(ts, tg, i, tile0, wend, len, t, li); uint32_t q;
@@ -178,13 +182,13 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_obj_parse(ObjJob *jobs) {
     if (k == 3) { const uint32_t nc = obj_face_corners(t, q, le); c[OBJ_TRI] += nc > 2 ? nc - 2 : 0; }
     else if (k >= 0) c[k]++;
   }
-  __shared__ uint32_t wsum[4][UVOL_BLOCK / 64];
-  uint32_t rank[4];
+  __shared__ uint32_t wsum[OBJ_NK][UVOL_BLOCK / 64];
+  uint32_t rank[OBJ_NK];
   { const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    uint32_t x[4];
-    for (int k = 0; k < 4; k++) { x[k] = c[k]; for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x[k], d); if (lane >= d) x[k] += y; } if (lane == 63) wsum[k][w] = x[k]; }
+    uint32_t x[OBJ_NK];
+    for (int k = 0; k < OBJ_NK; k++) { x[k] = c[k]; for (int d = 1; d < 64; d <<= 1) { const uint32_t y = __shfl_up(x[k], d); if (lane >= d) x[k] += y; } if (lane == 63) wsum[k][w] = x[k]; }
     __syncthreads();
-    for (int k = 0; k < 4; k++) { uint32_t base = 0; for (int j = 0; j < w; j++) base += wsum[k][j]; rank[k] = J.bcnt[(size_t)k * (J.nblk + 1) + blockIdx.x] + base + x[k] - c[k]; } }
+    for (int k = 0; k < OBJ_NK; k++) { uint32_t base = 0; for (int j = 0; j < w; j++) base += wsum[k][j]; rank[k] = J.bcnt[(size_t)k * (J.nblk + 1) + blockIdx.x] + base + x[k] - c[k]; } }
   if (!live) return;
   const uint32_t NP = J.tot[OBJ_V], NT = J.tot[OBJ_VT], NN = J.tot[OBJ_VN];
   for (uint32_t i = b0; i < b0 + OBJ_BPT && i < len; i++) {
@@ -232,9 +236,23 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_obj_parse(ObjJob *jobs) {
         }
         pr[0] = cur[0]; pr[1] = cur[1]; pr[2] = cur[2]; nc++;
       }
+    } else if (k == OBJ_MTL) {
+      if (J.mrec) J.mrec[rank[OBJ_MTL]] = make_uint2(i, rank[OBJ_TRI]);      // the triangles from here on take this line's material
+      rank[OBJ_MTL]++;
     }
   }
   (void)NP; (void)NT; (void)NN;
+}
+
+// material id per triangle (thread per triangle): the id of the last `usemtl` record ranked at or before it, 0 ahead of the first
+__global__ void __launch_bounds__(UVOL_BLOCK) k_obj_mat_expand(ObjJob *jobs) {
+  const ObjJob &J = jobs[blockIdx.y];
+  if (!J.fmat || J.status != 0) return;
+  const uint32_t t = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (t >= J.tot[OBJ_TRI]) return;
+  uint32_t lo = 0, hi = J.tot[OBJ_MTL];                                     // records [0, lo) are ranked at or before t
+  while (lo < hi) { const uint32_t mid = (lo + hi) / 2; if (J.mrec[mid].y <= t) lo = mid + 1; else hi = mid; }
+  J.fmat[t] = lo ? J.mid[lo - 1] : (uint8_t)0;
 }
 
 // ================================================================================================
@@ -264,9 +282,10 @@ void obj_destroy(uvol_ctx *ctx) {
 // n OBJ files as text (host memory) -> meshes_out[i] with DEVICE pointers into the context's slot `slot` (valid until that slot is parsed
 // into again); status[i]: UVOL_OK, UVOL_E_UNSUPPORTED (irregular text: parse it on the host), UVOL_E_INVALID (a face references a missing
 // vertex / no faces, as read_obj reports)
-int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *lens, int n, int slot, uvol_mesh *meshes_out, int *status) {
+int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *lens, int n, int slot, uvol_mesh *meshes_out, int *status, const uint8_t **fmat_out) {
   ObjState *S = ctx->obj;
   if (n <= 0) return UVOL_OK;
+  for (int i = 0; fmat_out && i < n; i++) fmat_out[i] = nullptr;
   if (slot < 0 || slot > 1) { ctx->set_error("uvol_parse_obj_batch_dev: slot must be 0 or 1"); return UVOL_E_INVALID; }
   if (!S->stream && uvol_make_stream(ctx, &S->stream) != hipSuccess) { ctx->set_error("ingest stream: creation failed"); return UVOL_E_HIP; }
   hipStream_t saved = ctx->stream; ctx->stream = S->stream;            // (uvol_ensure, uvol_upload_staged, Scope use ctx->stream)
@@ -278,7 +297,7 @@ int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *le
     if (!texts[i] || lens[i] == 0 || lens[i] > 0xfffffff0ull) { ctx->set_error("OBJ text %d: empty or larger than 4 GB", i); return UVOL_E_INVALID; }
     ObjJob &J = S->hjobs[i]; J.len = (uint32_t)lens[i]; J.nblk = (uint32_t)((lens[i] + OBJ_TILE - 1) / OBJ_TILE);
     toff[i] = ttot; ttot += (lens[i] + 255) & ~(size_t)255;
-    coff[i] = ctot; ctot += 4 * ((size_t)J.nblk + 1) * sizeof(uint32_t);
+    coff[i] = ctot; ctot += OBJ_NK * ((size_t)J.nblk + 1) * sizeof(uint32_t);
     max_blk = std::max(max_blk, J.nblk);
   }
   int rc;
@@ -293,7 +312,7 @@ int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *le
   ObjJob *dj = (ObjJob *)S->jobs.p;
   { uvol_ctx::Scope sc(ctx, "ingest.obj_count", (uint64_t)ttot);
     OLAUNCH(k_obj_count, dim3(max_blk, (unsigned)n), dim3(UVOL_BLOCK), dj);
-    OLAUNCH(k_obj_scan, dim3(4, (unsigned)n), dim3(UVOL_BLOCK), dj); }
+    OLAUNCH(k_obj_scan, dim3(OBJ_NK, (unsigned)n), dim3(UVOL_BLOCK), dj); }
   UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   UVOL_HIP_CHECK(ctx, hipMemcpy(S->hjobs.data(), dj, sizeof(ObjJob) * (size_t)n, hipMemcpyDeviceToHost));
   // the arrays, exactly sized
@@ -303,7 +322,13 @@ int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *le
     const ObjJob &J = S->hjobs[i];
     aoff[i] = atot;
     atot += a256(12 * (size_t)J.tot[OBJ_V] + 16) + a256(8 * (size_t)J.tot[OBJ_VT] + 16) + a256(12 * (size_t)J.tot[OBJ_VN] + 16) + 3 * a256(12 * (size_t)J.tot[OBJ_TRI] + 16);
+    if (fmat_out && J.tot[OBJ_MTL]) atot += a256((size_t)J.tot[OBJ_TRI] + 16);
   }
+  // the `usemtl` records of ALL files lie back to back (then one id per record, in the same order): one copy down, one copy up per call
+  std::vector<size_t> roff((size_t)n + 1, 0);
+  for (int i = 0; i < n; i++) roff[(size_t)i + 1] = roff[(size_t)i] + ((fmat_out && S->hjobs[i].tot[OBJ_MTL]) ? S->hjobs[i].tot[OBJ_MTL] : 0);
+  const size_t nrec = roff[(size_t)n], rec_at = atot, mid_at = rec_at + a256(8 * nrec + 16);
+  if (nrec) atot = mid_at + a256(nrec + 16);
   if ((rc = uvol_ensure(ctx, S->arrays[slot], atot))) return rc;
   for (int i = 0; i < n; i++) {
     ObjJob &J = S->hjobs[i]; uint8_t *b = (uint8_t *)S->arrays[slot].p + aoff[i];
@@ -312,7 +337,12 @@ int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *le
     J.nrm = (float *)b; b += a256(12 * (size_t)J.tot[OBJ_VN] + 16);
     J.ipos = (uint32_t *)b; b += a256(12 * (size_t)J.tot[OBJ_TRI] + 16);
     J.iuv = (uint32_t *)b; b += a256(12 * (size_t)J.tot[OBJ_TRI] + 16);
-    J.inrm = (uint32_t *)b;
+    J.inrm = (uint32_t *)b; b += a256(12 * (size_t)J.tot[OBJ_TRI] + 16);
+    J.mrec = nullptr; J.mid = nullptr; J.fmat = nullptr;
+    if (fmat_out && J.tot[OBJ_MTL]) {
+      J.fmat = b;
+      J.mrec = (uint2 *)((uint8_t *)S->arrays[slot].p + rec_at) + roff[(size_t)i]; J.mid = (uint8_t *)S->arrays[slot].p + mid_at + roff[(size_t)i];
+    }
     J.status = 0; J.no_uv = 0; J.no_n = 0;
   }
   UVOL_HIP_CHECK(ctx, hipMemcpyAsync(dj, S->hjobs.data(), sizeof(ObjJob) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
@@ -321,6 +351,40 @@ int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *le
   UVOL_HIP_CHECK(ctx, hipGetLastError());
   UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
   UVOL_HIP_CHECK(ctx, hipMemcpy(S->hjobs.data(), dj, sizeof(ObjJob) * (size_t)n, hipMemcpyDeviceToHost));
+  // material ids: the few `usemtl` records come back (one copy for the whole call), their names are resolved from the text the caller
+  // holds (ids by first appearance, from 0), one id per record goes up (one copy) and the runs are expanded to one byte per triangle
+  if (fmat_out && nrec) {
+    auto sp = [](uint8_t c) { return c == ' ' || c == '\t' || c == '\r'; };
+    std::vector<uint2> recs(nrec); std::vector<uint8_t> idv(nrec, 0); std::vector<std::string> names; uint32_t max_tri = 0; bool any = false;
+    UVOL_HIP_CHECK(ctx, hipMemcpy(recs.data(), (uint8_t *)S->arrays[slot].p + rec_at, sizeof(uint2) * nrec, hipMemcpyDeviceToHost));
+    for (int i = 0; i < n; i++) {
+      ObjJob &J = S->hjobs[i];
+      if (!J.fmat || J.status != 0) { J.fmat = nullptr; continue; }
+      const uint32_t nm = J.tot[OBJ_MTL];
+      const uint2 *rec = recs.data() + roff[(size_t)i]; uint8_t *ids = idv.data() + roff[(size_t)i]; names.clear();
+      const uint8_t *t = texts[i]; const size_t len = lens[i];
+      for (uint32_t r = 0; r < nm; r++) {
+        size_t a = rec[r].x, e = a; while (e < len && t[e] != '\n') e++;
+        while (a < e && sp(t[a])) a++;
+        a += 7; while (a < e && sp(t[a])) a++;                                // "usemtl" + its blank (k_obj_parse classified the line)
+        while (e > a && sp(t[e - 1])) e--;
+        const std::string name(a < e ? (const char *)t + a : "", a < e ? e - a : 0); size_t k = 0;
+        while (k < names.size() && names[k] != name) k++;
+        if (k == names.size()) names.push_back(name);
+        ids[r] = (uint8_t)k;
+      }
+      if (names.size() > 256) { fprintf(stderr, "OBJ text %d: %zu material names do not fit an 8-bit id: the material attribute is dropped\n", i, names.size()); J.fmat = nullptr; continue; }
+      max_tri = std::max(max_tri, J.tot[OBJ_TRI]); any = true;
+    }
+    if (any) {
+      UVOL_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)S->arrays[slot].p + mid_at, idv.data(), nrec, hipMemcpyHostToDevice, ctx->stream));
+      UVOL_HIP_CHECK(ctx, hipMemcpyAsync(dj, S->hjobs.data(), sizeof(ObjJob) * (size_t)n, hipMemcpyHostToDevice, ctx->stream));
+      { uvol_ctx::Scope sc(ctx, "ingest.obj_materials", 0);
+        OLAUNCH(k_obj_mat_expand, dim3(uvol_blocks(max_tri), (unsigned)n), dim3(UVOL_BLOCK), dj); }
+      UVOL_HIP_CHECK(ctx, hipGetLastError());
+      UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+    }
+  }
   ctx->resolve_profile();
   int worst = UVOL_OK;
   for (int i = 0; i < n; i++) {
@@ -332,6 +396,7 @@ int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *le
       M.pos = J.pos; M.n_pos = J.tot[OBJ_V]; M.idx_pos = J.ipos; M.n_faces = J.tot[OBJ_TRI];
       if (!J.no_uv && J.tot[OBJ_VT]) { M.uv = J.uv; M.n_uv = J.tot[OBJ_VT]; M.idx_uv = J.iuv; }
       if (!J.no_n && J.tot[OBJ_VN]) { M.nrm = J.nrm; M.n_nrm = J.tot[OBJ_VN]; M.idx_nrm = J.inrm; }
+      if (fmat_out) fmat_out[i] = J.fmat;
     } else if (st == UVOL_E_UNSUPPORTED) ctx->set_error("OBJ text %d: a number or line the device parser leaves to the host (more than 19 digits, inf / nan, a value on a float rounding boundary, an incomplete `v` line)", i);
     else ctx->set_error("OBJ text %d: %s", i, J.status == OBJ_E_BADFACE ? "face references a missing vertex" : "no faces");
     if (status) status[i] = st;

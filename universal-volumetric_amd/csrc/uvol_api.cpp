@@ -307,14 +307,17 @@ int uvol_trim(uvol_ctx *ctx) {
 // defer = the enqueue form: the call's groups are submitted and completed lazily (by the worker when its queue runs empty, or when a
 // later call needs the lane), so that consecutive enqueued calls overlap on the device
 static int encode_batch_common(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool dev,
-                               uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool defer = false) {
+                               uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool defer = false, const uint8_t *const *mats = nullptr) {
   if (!ctx || !meshes || n < 0 || !outs || !caps || !out_lens) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
+  { bool any = false; for (int i = 0; mats && i < n; i++) any = any || mats[i] != nullptr; if (!any) mats = nullptr; }
+  // stock draco_encoder's sequential connectivity (level 0) codes every attribute per point: the material attribute is not built for it
+  if (mats && ctx->prm.draco_compression_level == 0) { ctx->set_error("material ids with DRACO_COMPRESSION_LEVEL 0 (sequential connectivity) are not supported"); return UVOL_E_UNSUPPORTED; }
   const int mb = ctx->prm.max_batch;
   for (int b0 = 0; b0 < n; b0 += mb) {
     const int nb = n - b0 < mb ? n - b0 : mb;
-    int rc = defer ? geo_encode_batch_begin(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, true)
-                   : geo_encode_batch(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr);
+    int rc = defer ? geo_encode_batch_begin(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, true, mats ? mats + b0 : nullptr, b0)
+                   : geo_encode_batch(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, mats ? mats + b0 : nullptr, b0);
     if (rc != UVOL_OK) return rc;
   }
   return UVOL_OK;
@@ -389,6 +392,45 @@ int uvol_encode_mesh_batch_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n, 
 }
 int uvol_encode_mesh_batch_dev_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
   return mesh_batch_async(ctx, meshes, n, true, outs, caps, out_lens, status);
+}
+// ---- material ids (GENERIC uint8 attribute): the batch entry points with one more parallel array ----
+int uvol_encode_mesh_batch_mat(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, int inputs_on_device,
+                               uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
+  UVOL_AFTER_ASYNC(ctx);
+  return encode_batch_common(ctx, meshes, n, inputs_on_device != 0, outs, caps, out_lens, status, false, face_material);
+}
+int uvol_encode_mesh_batch_mat_async(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, int inputs_on_device,
+                                     uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
+  if (!face_material) return mesh_batch_async(ctx, meshes, n, inputs_on_device != 0, outs, caps, out_lens, status);
+  if (!ctx || !meshes || n < 0 || !outs || !caps || !out_lens) return UVOL_E_INVALID;
+  const bool dev = inputs_on_device != 0;
+  try {
+    std::vector<uvol_mesh> m(meshes, meshes + n); std::vector<uint8_t *> o(outs, outs + n); std::vector<size_t> c(caps, caps + n);
+    std::vector<const uint8_t *> fm(face_material, face_material + n);
+    return async_push(ctx, [ctx, m = std::move(m), o = std::move(o), c = std::move(c), fm = std::move(fm), n, dev, out_lens, status]() {
+      return encode_batch_common(ctx, m.data(), n, dev, o.data(), c.data(), out_lens, status, true, fm.data()); });
+  } catch (...) { ctx->set_error("enqueue: out of memory on the host"); return UVOL_E_HIP; }
+}
+int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
+                               uvol_decoded_mesh *out, uint8_t *const *face_material, int *has_material, int *status) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx || !drc || !lens || n < 0 || !out) return UVOL_E_INVALID;
+  (void)hipSetDevice(ctx->device);
+  const int mb = ctx->prm.max_batch;
+  for (int b0 = 0; b0 < n; b0 += mb) {
+    const int nb = n - b0 < mb ? n - b0 : mb;
+    const int rc = geo_decode_batch(ctx, drc + b0, lens + b0, nb, out + b0, status ? status + b0 : nullptr, outputs_on_device != 0,
+                                    face_material ? face_material + b0 : nullptr, has_material ? has_material + b0 : nullptr);
+    if (rc != UVOL_OK) return rc;
+  }
+  return UVOL_OK;
+}
+int uvol_parse_obj_batch_dev_mat(uvol_ctx *ctx, const uint8_t *const *obj_text, const size_t *lens, int n, int slot, uvol_mesh *meshes_out,
+                                 const uint8_t **face_material_dev_out, int *status) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx || !obj_text || !lens || n < 0 || !meshes_out) return UVOL_E_INVALID;
+  (void)hipSetDevice(ctx->device);
+  return obj_parse_batch(ctx, obj_text, lens, n, slot, meshes_out, status, face_material_dev_out);
 }
 static int tex_segments_async(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height, bool dev,
                               uint8_t *const *outs, const size_t *caps, size_t *out_lens) {

@@ -231,24 +231,28 @@ static inline unsigned uvol_blocks(size_t n, unsigned bs = UVOL_BLOCK) { return 
 hipError_t uvol_make_stream(uvol_ctx *ctx, hipStream_t *out);
 int geo_create(uvol_ctx *ctx);
 void geo_destroy(uvol_ctx *ctx);
+// mats: nullptr, or one pointer per frame to its material ids (one byte per input face, where the frame's own arrays live), nullptr = none;
+// frame0: index of meshes[0] in the caller's arrays (per-frame messages name the caller's frame)
 int geo_encode_batch(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool inputs_on_device,
-                     uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
+                     uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, const uint8_t *const *mats = nullptr, int frame0 = 0);
 // enqueue form: the groups of the call are submitted to the context's lanes and completed by geo_flush (or when a later call needs the lane)
 int geo_encode_batch_begin(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool inputs_on_device,
-                           uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool split);
+                           uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool split, const uint8_t *const *mats = nullptr, int frame0 = 0);
 int geo_flush(uvol_ctx *ctx);
 int geo_trim(uvol_ctx *ctx);
 // GPU-resident form: one group on lane 0, ordered after `producer`, bitstreams packed into the caller's device buffer
 int geo_encode_batch_dev_out(uvol_ctx *ctx, const uvol_mesh *meshes, int n, hipStream_t producer, uint8_t *dev_out, size_t dev_cap, size_t *out_offs, size_t *out_lens, int *status);
 int geodec_create(uvol_ctx *ctx);
 void geodec_destroy(uvol_ctx *ctx);
-int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool outputs_on_device = false);
+// face_material / has_material: uvol_decode_mesh_batch_mat (nullptr: not asked for)
+int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool outputs_on_device = false,
+                     uint8_t *const *face_material = nullptr, int *has_material = nullptr);
 int texdec_create(uvol_ctx *ctx);
 void texdec_destroy(uvol_ctx *ctx);
 int tex_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uint8_t *const *rgba, size_t layer_cap, bool outputs_on_device, int target, int *status = nullptr);
 int obj_create(uvol_ctx *ctx);
 void obj_destroy(uvol_ctx *ctx);
-int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *lens, int n, int slot, uvol_mesh *meshes_out, int *status);
+int obj_parse_batch(uvol_ctx *ctx, const uint8_t *const *texts, const size_t *lens, int n, int slot, uvol_mesh *meshes_out, int *status, const uint8_t **face_material_dev_out = nullptr);
 int png_create(uvol_ctx *ctx);
 void png_destroy(uvol_ctx *ctx);
 int png_order_before(uvol_ctx *ctx, hipStream_t stream, const uint8_t *const *layers, size_t n_layers);

@@ -29,8 +29,17 @@ int main(int argc, char **argv) {
   um.pos = m.pos.data(); um.n_pos = (uint32_t)m.pos.size() / 3; um.idx_pos = m.idx_pos.data(); um.n_faces = (uint32_t)m.idx_pos.size() / 3;
   if (!m.uv.empty()) { um.uv = m.uv.data(); um.n_uv = (uint32_t)m.uv.size() / 2; um.idx_uv = m.idx_uv.data(); }
   if (!m.nrm.empty()) { um.nrm = m.nrm.data(); um.n_nrm = (uint32_t)m.nrm.size() / 3; um.idx_nrm = m.idx_nrm.data(); }
-  std::vector<uint8_t> buf(uvol_mesh_bound(&um)); size_t len = 0;
-  const int rc = uvol_encode_mesh(ctx, &um, buf.data(), buf.size(), &len);
+  // `usemtl` lines: the GENERIC uint8 material attribute stock draco_encoder adds (uvol_encode_mesh_batch_mat).  Not at -cl 0 (sequential
+  // connectivity), and not where two materials meet at a vertex: such a file is written without the attribute, and stderr says so.
+  const uint8_t *fm = m.face_mat.empty() ? nullptr : m.face_mat.data();
+  if (fm && prm.draco_compression_level == 0) { std::fprintf(stderr, "draco_encoder (uvol shim): %s: -cl 0: the material attribute (usemtl) is left out\n", in.c_str()); fm = nullptr; }
+  std::vector<uint8_t> buf(fm ? uvol_mesh_bound_mat(&um) : uvol_mesh_bound(&um)); size_t len = 0;
+  uint8_t *op = buf.data(); const size_t cap = buf.size(); int st = UVOL_OK;
+  int rc = uvol_encode_mesh_batch_mat(ctx, &um, &fm, 1, 0, &op, &cap, &len, &st);
+  if (rc == UVOL_OK && st == UVOL_E_UNSUPPORTED && fm) {
+    std::fprintf(stderr, "draco_encoder (uvol shim): %s: materials meet at shared vertices (interior material seams): encoded without the material attribute\n", in.c_str());
+    rc = uvol_encode_mesh(ctx, &um, buf.data(), buf.size(), &len);
+  } else if (rc == UVOL_OK) rc = st;
   if (rc != UVOL_OK) { std::fprintf(stderr, "Failed to encode the mesh: %s\n", uvol_last_error(ctx)); uvol_ctx_destroy(ctx); return 3; }
   uvol_ctx_destroy(ctx);
   if (!uvolh::write_file(out, buf.data(), len)) { std::fprintf(stderr, "Failed to create the output file.\n"); return 4; }

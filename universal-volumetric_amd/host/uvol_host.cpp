@@ -254,10 +254,19 @@ static inline bool fast_float(const char *&q, const char *le, float &out) {
   if (!(std::fabs(f) >= 1.17549435e-38f) && mant != 0) return false;       // subnormal floats round differently: strtof
   out = neg ? -f : f; q = p; return true;
 }
+bool obj_usemtl_name(const char *ln, const char *le, const char *&nb, const char *&ne) {
+  auto sp = [](char c) { return c == ' ' || c == '\t' || c == '\r'; };
+  while (ln < le && sp(*ln)) ln++;
+  if (le - ln < 7 || std::memcmp(ln, "usemtl", 6) != 0 || !(ln[6] == ' ' || ln[6] == '\t')) return false;
+  ln += 7; while (ln < le && sp(*ln)) ln++;
+  while (le > ln && sp(le[-1])) le--;
+  nb = ln; ne = le; return true;
+}
 bool read_obj(const std::string &path, ObjMesh &m, std::string &err, IngestScratch *scratch) {
   IngestScratch local; IngestScratch &S = scratch ? *scratch : local;
   std::vector<uint8_t> &d = S.file; if (!read_file(path, d)) { err = "cannot read " + path; return false; }
-  m.pos.clear(); m.uv.clear(); m.nrm.clear(); m.idx_pos.clear(); m.idx_uv.clear(); m.idx_nrm.clear();      // capacity is kept
+  m.pos.clear(); m.uv.clear(); m.nrm.clear(); m.idx_pos.clear(); m.idx_uv.clear(); m.idx_nrm.clear(); m.face_mat.clear();      // capacity is kept
+  std::vector<std::string> mtl_names; size_t mtl_cur = 0; bool mtl_any = false;
   const char *p = (const char *)d.data(), *e = p + d.size();
   bool has_uv = true, has_n = true; long nfaces = 0;
   std::vector<long> &fv = S.fv, &ft = S.ft, &fn = S.fn;
@@ -269,7 +278,7 @@ bool read_obj(const std::string &path, ObjMesh &m, std::string &err, IngestScrat
       while (ln < q && (*ln == ' ' || *ln == '\t')) ln++;
       if (ln + 1 < q) { if (ln[0] == 'v') { if (ln[1] == ' ' || ln[1] == '\t') nv++; else if (ln[1] == 't') nt++; else if (ln[1] == 'n') nn++; } else if (ln[0] == 'f') nfl++; }
     }
-    m.pos.reserve(3 * nv); m.uv.reserve(2 * nt); m.nrm.reserve(3 * nn); m.idx_pos.reserve(3 * nfl + 64); m.idx_uv.reserve(3 * nfl + 64); m.idx_nrm.reserve(3 * nfl + 64);
+    m.pos.reserve(3 * nv); m.uv.reserve(2 * nt); m.nrm.reserve(3 * nn); m.idx_pos.reserve(3 * nfl + 64); m.idx_uv.reserve(3 * nfl + 64); m.idx_nrm.reserve(3 * nfl + 64); m.face_mat.reserve(nfl + 64);
   }
   auto skip_sp = [&](const char *&q) { while (q < e && (*q == ' ' || *q == '\t' || *q == '\r')) q++; };
   auto num = [&](const char *&q, const char *le, float &o) {
@@ -316,10 +325,22 @@ bool read_obj(const std::string &path, ObjMesh &m, std::string &err, IngestScrat
           if (fn[t] < 0 || fn[t] >= (long)m.nrm.size() / 3) has_n = false;
           m.idx_nrm.push_back(fn[t] < 0 ? 0u : (uint32_t)fn[t]);
         }
+        m.face_mat.push_back((uint8_t)mtl_cur);                             // every triangle of a fanned polygon gets its polygon's id
         nfaces++;
       }
     }
+    else if (q < le && q[0] == 'u') {
+      const char *nb, *ne;
+      if (obj_usemtl_name(q, le, nb, ne)) {
+        const std::string name(nb, ne); size_t k = 0;
+        while (k < mtl_names.size() && mtl_names[k] != name) k++;
+        if (k == mtl_names.size()) mtl_names.push_back(name);
+        mtl_cur = k; mtl_any = true;
+      }
+    }
   }
+  if (!mtl_any) m.face_mat.clear();
+  else if (mtl_names.size() > 256) { std::fprintf(stderr, "%s: %zu material names do not fit an 8-bit id: the material attribute is dropped\n", path.c_str(), mtl_names.size()); m.face_mat.clear(); }
   if (!nfaces || m.pos.empty()) { err = path + ": no faces"; return false; }
   if (!has_uv || m.uv.empty()) { m.uv.clear(); m.idx_uv.clear(); }
   if (!has_n || m.nrm.empty()) { m.nrm.clear(); m.idx_nrm.clear(); }
@@ -577,6 +598,13 @@ int uvolh_read_obj_positions(const char *path, float *pos, size_t cap_floats) {
   uvolh::ObjMesh m; std::string err; if (!uvolh::read_obj(path, m, err)) return -1;
   if (m.pos.size() > cap_floats) return -2;
   std::memcpy(pos, m.pos.data(), m.pos.size() * sizeof(float)); return (int)(m.pos.size() / 3);
+}
+// test hook: read_obj's material id per triangle: their count (0: the file has no usemtl line), -1 on a read error
+long uvolh_read_obj_materials(const char *path, unsigned char *out, size_t cap) {
+  uvolh::ObjMesh m; std::string err; if (!uvolh::read_obj(path, m, err)) return -1;
+  if (m.face_mat.size() > cap) return -2;
+  if (!m.face_mat.empty()) std::memcpy(out, m.face_mat.data(), m.face_mat.size());
+  return (long)m.face_mat.size();
 }
 // test hook: every array read_obj produces (the device parser of csrc/obj_ingest.hip must agree with it bit for bit); counts6 = {n_pos, n_uv,
 // n_nrm, faces, faces with uv indices, faces with normal indices}; buffers may be NULL (counts only)

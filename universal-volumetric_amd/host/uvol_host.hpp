@@ -47,7 +47,11 @@ bool load_config(const std::string &json_text, Config &c, std::string &err);
 std::string config_template();                                          // `create-template` (scripts/Encoder.py:163-186)
 
 // ---- ingest ----
-struct ObjMesh { std::vector<float> pos, uv, nrm; std::vector<uint32_t> idx_pos, idx_uv, idx_nrm; };
+// face_mat: one material id per triangle when the file has a `usemtl` line (ids by first appearance of the name, from 0; faces ahead of the
+// first `usemtl` take id 0; `mtllib` files are not read), else empty; also empty - with one line on stderr - for a file with more than 256 names
+struct ObjMesh { std::vector<float> pos, uv, nrm; std::vector<uint32_t> idx_pos, idx_uv, idx_nrm; std::vector<uint8_t> face_mat; };
+// the name of a `usemtl NAME` line [ln, le): blanks (space, tab, CR) around it dropped; false: not such a line
+bool obj_usemtl_name(const char *ln, const char *le, const char *&nb, const char *&ne);
 // Buffers an ingest worker keeps between files.  A 100 k-vertex OBJ + a 2048^2 PNG need ~70 MB of temporaries; allocated afresh
 // per file they are ~70 MB of new pages to fault in per frame, and 128 ingest threads of one process faulting at once serialise
 // on the address-space lock (a file took 300 ms instead of 43).  read_obj / read_png also REUSE the capacity of the ObjMesh /

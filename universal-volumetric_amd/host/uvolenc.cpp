@@ -141,6 +141,7 @@ int main(int argc, char **argv) {
                       std::vector<std::vector<uint8_t>> text;              // device parser: the files as they are
                       uint8_t *pin = nullptr; size_t pin_cap = 0; std::vector<size_t> toff, tlen;      // --pinned-text: ... read into ONE page-locked slab (uvol_host_alloc): the upload is DMA from where the text lies
                       ~GeoBatch() { if (pin) uvol_host_free(pin); }
+                      std::vector<const uint8_t *> fm;                     // material ids per frame (`usemtl` lines): device / host memory like the frame's arrays, nullptr = none
                       std::vector<uvol_mesh> um; std::vector<uint8_t *> op; std::vector<size_t> caps, lens; std::vector<int> st, pst; };
     for (int g = 0; g < n_gpus; g++) geo_threads.emplace_back([&, g] {
       const std::vector<std::string> &files = obj_files;
@@ -191,12 +192,13 @@ int main(int argc, char **argv) {
       auto prepare = [&](GeoBatch &Bt, int slot) -> bool {
         const size_t nb = Bt.nb, b0 = Bt.b0;
         if (Bt.bad >= 0) { std::printf("Failed to compress %s\n%s\n", files[b0 + (size_t)Bt.bad].c_str(), Bt.err.c_str()); geo_failed = (int)(b0 + (size_t)Bt.bad); return false; }
+        Bt.fm.assign(nb, nullptr);
         Bt.um.assign(nb, uvol_mesh{}); Bt.op.assign(nb, nullptr); Bt.caps.assign(nb, 0); Bt.lens.assign(nb, 0); Bt.st.assign(nb, 0); Bt.pst.assign(nb, 0);
         if (Bt.outs.size() < nb) { Bt.outs.resize(nb); Bt.ocap.resize(nb, 0); }
         if (!host_obj) {
           std::vector<const uint8_t *> tp(nb); std::vector<size_t> tl(nb);
           for (size_t k = 0; k < nb; k++) { if (pinned_text) { tp[k] = Bt.pin + Bt.toff[k]; tl[k] = Bt.tlen[k]; } else { tp[k] = Bt.text[k].data(); tl[k] = Bt.text[k].size(); } }
-          const int rc = uvol_parse_obj_batch_dev(pctxs[g], tp.data(), tl.data(), (int)nb, slot, Bt.um.data(), Bt.pst.data());
+          const int rc = uvol_parse_obj_batch_dev_mat(pctxs[g], tp.data(), tl.data(), (int)nb, slot, Bt.um.data(), Bt.fm.data(), Bt.pst.data());
           if (rc != UVOL_OK) { std::printf("Failed to compress %s\n%s\n", files[b0].c_str(), uvol_last_error(pctxs[g])); geo_failed = (int)b0; return false; }
           if (Bt.ms.size() < nb) Bt.ms.resize(nb);
           for (size_t k = 0; k < nb; k++) {
@@ -213,8 +215,11 @@ int main(int argc, char **argv) {
             m.pos = o.pos.data(); m.n_pos = (uint32_t)o.pos.size() / 3; m.idx_pos = o.idx_pos.data(); m.n_faces = (uint32_t)o.idx_pos.size() / 3;
             if (!o.uv.empty()) { m.uv = o.uv.data(); m.n_uv = (uint32_t)o.uv.size() / 2; m.idx_uv = o.idx_uv.data(); }
             if (!o.nrm.empty()) { m.nrm = o.nrm.data(); m.n_nrm = (uint32_t)o.nrm.size() / 3; m.idx_nrm = o.idx_nrm.data(); }
+            Bt.fm[k] = o.face_mat.empty() ? nullptr : o.face_mat.data();
           }
-          Bt.caps[k] = uvol_mesh_bound(&m); if (Bt.ocap[k] < Bt.caps[k]) { Bt.outs[k].reset(new uint8_t[Bt.caps[k]]); Bt.ocap[k] = Bt.caps[k]; } Bt.op[k] = Bt.outs[k].get();   // (not zero-filled: the bound is a worst case)
+          // DRACO_COMPRESSION_LEVEL 0 (sequential connectivity) has no material attribute here: the frame is encoded without it
+          if (Bt.fm[k] && cfg.compression_level == 0) { std::fprintf(stderr, "%s: DRACO_COMPRESSION_LEVEL 0: the material attribute (usemtl) is left out\n", files[b0 + k].c_str()); Bt.fm[k] = nullptr; }
+          Bt.caps[k] = Bt.fm[k] ? uvol_mesh_bound_mat(&m) : uvol_mesh_bound(&m); if (Bt.ocap[k] < Bt.caps[k]) { Bt.outs[k].reset(new uint8_t[Bt.caps[k]]); Bt.ocap[k] = Bt.caps[k]; } Bt.op[k] = Bt.outs[k].get();   // (not zero-filled: the bound is a worst case)
         }
         return true;
       };
@@ -224,7 +229,7 @@ int main(int argc, char **argv) {
         for (size_t a = 0; a < nb;) {
           const bool dev = !host_obj && Bt.pst[a] == UVOL_OK; size_t b = a + 1;
           while (b < nb && (!host_obj && Bt.pst[b] == UVOL_OK) == dev) b++;
-          const int rc = (dev ? uvol_encode_mesh_batch_dev_async : uvol_encode_mesh_batch_async)(ctxs[g], Bt.um.data() + a, (int)(b - a), Bt.op.data() + a, Bt.caps.data() + a, Bt.lens.data() + a, Bt.st.data() + a);
+          const int rc = uvol_encode_mesh_batch_mat_async(ctxs[g], Bt.um.data() + a, Bt.fm.data() + a, (int)(b - a), dev ? 1 : 0, Bt.op.data() + a, Bt.caps.data() + a, Bt.lens.data() + a, Bt.st.data() + a);
           if (rc != UVOL_OK) return rc;
           a = b;
         }
@@ -248,6 +253,13 @@ int main(int argc, char **argv) {
         const double te2 = now_ms();
         if (rc == UVOL_OK) rc = uvol_sync(ctxs[g]);
         if (rc != UVOL_OK) { std::printf("Failed to compress %s\n%s\n", files[b0].c_str(), uvol_last_error(ctxs[g])); if (geo_failed < 0) geo_failed = (int)b0; break; }
+        // a frame refused because two of its materials meet at a vertex (an interior material seam) is encoded again without the attribute
+        for (size_t k = 0; k < nb; k++) if (Bt.st[k] == UVOL_E_UNSUPPORTED && Bt.fm[k]) {
+          std::fprintf(stderr, "%s: materials meet at shared vertices (interior material seams): encoded without the material attribute\n", files[b0 + k].c_str());
+          const bool dev = !host_obj && Bt.pst[k] == UVOL_OK; int st1 = UVOL_OK;
+          const int r1 = uvol_encode_mesh_batch_mat(ctxs[g], &Bt.um[k], nullptr, 1, dev ? 1 : 0, &Bt.op[k], &Bt.caps[k], &Bt.lens[k], &st1);
+          Bt.st[k] = r1 != UVOL_OK ? r1 : st1;
+        }
         for (size_t k = 0; k < nb; k++) if (Bt.st[k] != UVOL_OK) { std::printf("Failed to compress %s\n", files[b0 + k].c_str()); if (geo_failed < 0 || (int)(b0 + k) < geo_failed) geo_failed = (int)(b0 + k); break; }   // scripts/Encoder.py:263-266
         if (geo_failed >= 0 && !nxt_ok) break;
         if (geo_failed >= 0 && (size_t)geo_failed >= b0 && (size_t)geo_failed < b0 + nb) break;

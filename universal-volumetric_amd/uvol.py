@@ -40,7 +40,8 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_encode_texture_segment_dev", "uvol_encode_texture_segments", "uvol_encode_texture_segments_dev",
            "uvol_ktx2_info", "uvol_decode_texture_segments", "uvol_decode_texture_segments_dev", "uvol_transcode_texture_segments_etc1", "uvol_transcode_texture_segments_bc7", "uvol_transcode_texture_segments_etc2_rgba", "uvol_transcode_texture_segments_astc", "uvol_drc_info", "uvol_decode_mesh_batch", "uvol_profile_enable", "uvol_profile_reset", "uvol_profile_count",
            "uvol_profile_get", "uvol_encode_texture_segments_st", "uvol_transcode_texture_segments_st",
-           "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status"]
+           "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status",
+           "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat"]
 
 
 def load(path=None):
@@ -60,6 +61,13 @@ def load(path=None):
     for nm in ("uvol_encode_mesh_batch", "uvol_encode_mesh_batch_dev", "uvol_encode_mesh_batch_async", "uvol_encode_mesh_batch_dev_async"):
         getattr(L, nm).argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
                                    C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.uvol_mesh_bound_mat.argtypes = [C.POINTER(Mesh)]; L.uvol_mesh_bound_mat.restype = C.c_size_t
+    for nm in ("uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async"):
+        getattr(L, nm).argtypes = [C.c_void_p, C.POINTER(Mesh), C.POINTER(C.c_void_p), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t),
+                                   C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+    L.uvol_decode_mesh_batch_mat.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodedMesh),
+                                             C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.uvol_parse_obj_batch_dev_mat.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.uvol_texture_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_int]; L.uvol_texture_bound.restype = C.c_size_t
     for nm in ("uvol_encode_texture_segment", "uvol_encode_texture_segment_dev"):
         getattr(L, nm).argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_void_p,
@@ -183,22 +191,49 @@ class Codec:
             m.nrm = nrm.ctypes.data; m.n_nrm = len(nrm); m.idx_nrm = idx_nrm.ctypes.data
         return m, (pos, uv, nrm, idx_pos, idx_uv, idx_nrm)
 
+    @staticmethod
+    def _mesh_host_mat(face_mat=None, **f):
+        """_mesh_host of a frame dict that may carry "face_mat" (one uint8 material id per face) -> (Mesh, its arrays, the id array or None)."""
+        m, keep = Codec._mesh_host(**f)
+        face_mat = None if face_mat is None else np.ascontiguousarray(face_mat, dtype=np.uint8).reshape(-1)
+        if face_mat is not None and len(face_mat) != m.n_faces:
+            raise ValueError("face_mat: one material id per face")
+        return m, keep, face_mat
+
+    @staticmethod
+    def _mat_ptrs(mats):
+        """The parallel face_material array of the _mat entry points (None when no frame has ids: the plain entry points are called)."""
+        if all(a is None for a in mats):
+            return None
+        return (C.c_void_p * len(mats))(*[(None if a is None else a.ctypes.data) for a in mats])
+
     def mesh_workspace(self, pos, idx_pos, uv=None, idx_uv=None, nrm=None, idx_nrm=None) -> int:
         """Device bytes one frame of these dimensions holds while in flight."""
         m, keep = self._mesh_host(pos, idx_pos, uv, idx_uv, nrm, idx_nrm)
         return int(self.L.uvol_mesh_workspace(self.h, C.byref(m)))
 
-    def encode_mesh(self, pos, idx_pos, uv=None, idx_uv=None, nrm=None, idx_nrm=None) -> bytes:
-        return self.encode_mesh_batch([dict(pos=pos, idx_pos=idx_pos, uv=uv, idx_uv=idx_uv, nrm=nrm, idx_nrm=idx_nrm)])[0]
+    def encode_mesh(self, pos, idx_pos, uv=None, idx_uv=None, nrm=None, idx_nrm=None, face_mat=None) -> bytes:
+        return self.encode_mesh_batch([dict(pos=pos, idx_pos=idx_pos, uv=uv, idx_uv=idx_uv, nrm=nrm, idx_nrm=idx_nrm, face_mat=face_mat)])[0]
 
     def encode_mesh_batch(self, frames, raise_on_error=True, views=False):
-        """frames: list of dicts(pos, idx_pos[, uv, idx_uv, nrm, idx_nrm]) of host arrays -> list of .drc bytes (views=True: numpy views
-        of this codec's output buffers, valid until the next call)."""
+        """frames: list of dicts(pos, idx_pos[, uv, idx_uv, nrm, idx_nrm, face_mat]) of host arrays -> list of .drc bytes (views=True: numpy
+        views of this codec's output buffers, valid until the next call).  face_mat: one uint8 material id per face (the OBJ `usemtl`
+        attribute, uvol_encode_mesh_batch_mat); a frame in which two materials meet at a vertex fails alone with UVOL_E_UNSUPPORTED."""
         n = len(frames)
-        meshes = (Mesh * n)(); keep = []
+        meshes = (Mesh * n)(); keep = []; fms = []
         for i, f in enumerate(frames):
-            m, k = self._mesh_host(**f); meshes[i] = m; keep.append(k)
-        return self._run_batch(self.L.uvol_encode_mesh_batch, meshes, n, raise_on_error, views)
+            m, k, fm = self._mesh_host_mat(**f); meshes[i] = m; keep.append(k); fms.append(fm)
+        mats = self._mat_ptrs(fms)
+        if mats is None:
+            return self._run_batch(self.L.uvol_encode_mesh_batch, meshes, n, raise_on_error, views)
+        fn = lambda h, ms, nn, outs, caps, lens, st: self.L.uvol_encode_mesh_batch_mat(h, ms, mats, nn, 0, outs, caps, lens, st)
+        return self._run_batch(fn, meshes, n, raise_on_error, views, bound=self.L.uvol_mesh_bound_mat)
+
+    def encode_mesh_batch_dev_mat(self, meshes, mats, raise_on_error=True, views=False):
+        """As encode_mesh_batch_dev, with material ids resident in HBM: mats = list of device pointers (ints, None = no ids for that frame)."""
+        mp = (C.c_void_p * len(meshes))(*[(None if p is None else int(p)) for p in mats])
+        fn = lambda h, ms, nn, outs, caps, lens, st: self.L.uvol_encode_mesh_batch_mat(h, ms, mp, nn, 1, outs, caps, lens, st)
+        return self._run_batch(fn, meshes, len(meshes), raise_on_error, views, bound=self.L.uvol_mesh_bound_mat)
 
     def encode_mesh_batch_dev(self, meshes, raise_on_error=True, views=False):
         """meshes: ctypes array of Mesh holding DEVICE pointers (inputs resident in HBM).  views=True: numpy views of this
@@ -273,22 +308,26 @@ class Codec:
         returns `bytes`; slot=k: the output buffers of slot k are re-used by every call with that slot and finish() returns numpy views into
         them (two slots let consecutive enqueued calls overlap without a buffer set - and its page faults - per call)."""
         n = len(frames)
-        meshes = (Mesh * n)(); keep = []
+        meshes = (Mesh * n)(); keep = []; fms = []
         for i, f in enumerate(frames):
-            m, k = self._mesh_host(**f); meshes[i] = m; keep.append(k)
+            m, k, fm = self._mesh_host_mat(**f); meshes[i] = m; keep.append(k); fms.append(fm)
         caps = (C.c_size_t * n)(); lens = (C.c_size_t * n)(); st = (C.c_int * n)(); outs = (C.c_void_p * n)()
         bufs = [] if slot is None else self.__dict__.setdefault("_slot_bufs", {}).setdefault(("host", slot), [])
         while len(bufs) < n:
             bufs.append(np.empty(0, dtype=np.uint8))
+        mats = self._mat_ptrs(fms)
         for i in range(n):
-            cap = self.L.uvol_mesh_bound(C.byref(meshes[i]))
+            cap = (self.L.uvol_mesh_bound if mats is None else self.L.uvol_mesh_bound_mat)(C.byref(meshes[i]))
             if bufs[i].size < cap:
                 bufs[i] = np.empty(cap, dtype=np.uint8)
             caps[i] = cap; outs[i] = bufs[i].ctypes.data
-        rc = self.L.uvol_encode_mesh_batch_async(self.h, meshes, n, outs, caps, lens, st)
+        if mats is None:
+            rc = self.L.uvol_encode_mesh_batch_async(self.h, meshes, n, outs, caps, lens, st)
+        else:
+            rc = self.L.uvol_encode_mesh_batch_mat_async(self.h, meshes, mats, n, 0, outs, caps, lens, st)
         if rc != UVOL_OK:
             raise UvolError(f"encode_mesh_batch_async rc={rc}: {self.error()}")
-        self._pending = getattr(self, "_pending", []) + [("mesh" if slot is None else "mesh_views", n, bufs, lens, st, keep, meshes)]
+        self._pending = getattr(self, "_pending", []) + [("mesh" if slot is None else "mesh_views", n, bufs, lens, st, (keep, fms, mats), meshes)]
 
     def start_mesh_batch_dev(self, meshes, slot=0):
         """Enqueues uvol_encode_mesh_batch_dev_async for a ctypes array of Mesh holding DEVICE pointers.  The output buffers of `slot`
@@ -370,13 +409,14 @@ class Codec:
             raise e
         return res
 
-    def _run_batch(self, fn, meshes, n, raise_on_error, views=False):
+    def _run_batch(self, fn, meshes, n, raise_on_error, views=False, bound=None):
+        bound = bound or self.L.uvol_mesh_bound
         caps = (C.c_size_t * n)(); lens = (C.c_size_t * n)(); st = (C.c_int * n)(); outs = (C.c_void_p * n)()
         bufs = getattr(self, "_obufs", [])          # output buffers are kept between calls (no fresh pages to fault in per batch)
         while len(bufs) < n:
             bufs.append(np.empty(0, dtype=np.uint8))
         for i in range(n):
-            cap = self.L.uvol_mesh_bound(C.byref(meshes[i]))
+            cap = bound(C.byref(meshes[i]))
             if bufs[i].size < cap:
                 bufs[i] = np.empty(cap, dtype=np.uint8)
             caps[i] = cap; outs[i] = bufs[i].ctypes.data
@@ -561,7 +601,7 @@ class Codec:
             raise UvolError(f"decode_texture_segments_dev rc={rc}: {self.error()}")
 
     # ---- decode path (geometry half) ----
-    def decode_arena_bytes(self, files):
+    def decode_arena_bytes(self, files, materials=False):
         """Bytes of a PinnedArena that holds the output arrays of decode_mesh_batch(files, arena=...): capacities by uvol_drc_info (the counts
         are not known before the decode: 3 x faces values per attribute at most)."""
         tot = 0
@@ -569,12 +609,14 @@ class Codec:
             nf, mv = C.c_uint32(), C.c_uint32()
             if self.L.uvol_drc_info(bytes(f), len(f), C.byref(nf), C.byref(mv)) != UVOL_OK:
                 raise UvolError("not a .drc this decoder handles")
-            tot += mv.value * 32 + 3 * nf.value * 12 + 6 * 256
+            tot += mv.value * 32 + 3 * nf.value * 12 + 6 * 256 + ((nf.value + 256) if materials else 0)      # (materials: + one id per face)
         return tot + 4096
 
-    def decode_mesh_batch(self, files, raise_on_error=True, fetch=True, views=False, arena=None):
+    def decode_mesh_batch(self, files, raise_on_error=True, fetch=True, views=False, arena=None, materials=False):
         """files: list of .drc bytes -> list of dicts {pos [n,3], uv [n,2], nrm [n,3] float32 in decoding order,
-        idx_pos / idx_uv / idx_nrm [3*faces] uint32 entry index per corner}; absent attributes are None.
+        idx_pos / idx_uv / idx_nrm [3*faces] uint32 entry index per corner, face_mat [faces] uint8 material id per face}; absent attributes
+        (and face_mat of a file without a GENERIC uint8 one-component vertex attribute) are None.  face_mat is only there with materials=True
+        (uvol_decode_mesh_batch_mat: one more kernel and one more array per frame; size an arena with decode_arena_bytes(files, materials=True)).
         arena (a PinnedArena, with views=True): the output arrays are carved from it - outputs that all lie in uvol_host_alloc memory are written
         by the DMA engines where they are, without the library's staging buffers."""
         files = [bytes(f) for f in files]; n = len(files)
@@ -599,7 +641,14 @@ class Codec:
             for k, v in a.items():
                 setattr(m, k, v.ctypes.data if fetch else None)        # fetch=False: decode only, results stay on the device (timing)
         fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
-        rc = self.L.uvol_decode_mesh_batch(self.h, fp, ln, n, metas, st)
+        fmats = None; hm = (C.c_int * n)()
+        if fetch and materials:                # (with an arena the ids lie in it too: one pageable output would send the whole call through the staging buffers)
+            fmats = [mk((max(1, metas[i].cap_faces),), np.uint8) for i in range(n)]
+        if fmats is not None:
+            fmp = (C.c_void_p * n)(*[a.ctypes.data for a in fmats])
+            rc = self.L.uvol_decode_mesh_batch_mat(self.h, fp, ln, n, 0, metas, fmp, hm, st)
+        else:
+            rc = self.L.uvol_decode_mesh_batch(self.h, fp, ln, n, metas, st)
         if rc != UVOL_OK:
             raise UvolError(f"decode_mesh_batch rc={rc}: {self.error()}")
         res = []
@@ -614,7 +663,8 @@ class Codec:
                 res.append(dict(n_faces=m.n_faces, n_pos=m.n_pos, n_uv=m.n_uv, n_nrm=m.n_nrm)); continue
             cp = (lambda v: v) if views else (lambda v: v.copy())
             res.append({k: (cp(a[k][:cnt[k]]) if cnt[k] else None) for k in ("pos", "uv", "nrm")} |
-                       {"idx_" + k: (cp(a["idx_" + k][:3 * m.n_faces]) if cnt[k] else None) for k in ("pos", "uv", "nrm")} | {"n_faces": m.n_faces})
+                       {"idx_" + k: (cp(a["idx_" + k][:3 * m.n_faces]) if cnt[k] else None) for k in ("pos", "uv", "nrm")} | {"n_faces": m.n_faces} |
+                       ({"face_mat": (cp(fmats[i][:m.n_faces]) if hm[i] else None)} if fmats is not None else {}))
         return res
 
     # ---- measurement ----
