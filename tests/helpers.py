@@ -170,8 +170,53 @@ def bc7_decode_blocks(blocks, width, height):
     return out[:height, :width]
 
 
+def _raster_blocks(px, width, height):
+    """px [by, bx, 16, c] texels of every block in raster order -> image [height, width, c]."""
+    by, bx, _, c = px.shape
+    return px.reshape(by, bx, 4, 4, c).transpose(0, 2, 1, 3, 4).reshape(by * 4, bx * 4, c)[:height, :width]
+
+
 def bc1_decode_blocks(blocks, width, height, four_colour_always=False):
     """Independent BC1 (DXT1) colour-block decoder written from the format description: colour0 / colour1 as little-endian RGB565, 16 2-bit
+    indices in raster order from bit 0; colour0 > colour1 (or four_colour_always, as inside BC2 / BC3): palette c0, c1, (2 c0 + c1) / 3,
+    (c0 + 2 c1) / 3; otherwise c0, c1, (c0 + c1) / 2 and transparent black.  blocks [by, bx, 8] uint8 -> RGBA8 [height, width, 4].
+    All blocks at once (bc1_decode_blocks_scalar below is the same decoder one block at a time)."""
+    b = blocks.astype(np.int64)
+    c0 = b[..., 0] | (b[..., 1] << 8); c1 = b[..., 2] | (b[..., 3] << 8)
+
+    def rgb(c):
+        r, g, bl = c >> 11, (c >> 5) & 63, c & 31
+        return np.stack([(r << 3) | (r >> 2), (g << 2) | (g >> 4), (bl << 3) | (bl >> 2)], -1)
+    e0, e1 = rgb(c0), rgb(c1)
+    four = ((c0 > c1) | bool(four_colour_always))[..., None]
+    pal = np.stack([e0, e1, np.where(four, (2 * e0 + e1) // 3, (e0 + e1) // 2), np.where(four, (e0 + 2 * e1) // 3, 0)], -2)          # [by, bx, 4, 3]
+    pal = np.concatenate([pal, np.stack([np.full(four.shape, 255), np.full(four.shape, 255), np.full(four.shape, 255), np.where(four, 255, 0)], -2)], -1)
+    idx = b[..., 4] | (b[..., 5] << 8) | (b[..., 6] << 16) | (b[..., 7] << 24)
+    sel = (idx[..., None] >> (2 * np.arange(16))) & 3                                                                                     # [by, bx, 16]
+    px = np.take_along_axis(pal, sel[..., None], -2)
+    return _raster_blocks(px, width, height).astype(np.uint8)
+
+
+def bc3_decode_blocks(blocks, width, height):
+    """Independent BC3 (DXT5) decoder: a BC4 alpha block (alpha0, alpha1, 16 3-bit indices in raster order from bit 0; alpha0 > alpha1: six
+    interpolated values ((8 - j) a0 + (j - 1) a1) / 7 for index j = 2 .. 7, else four interpolated values, then 0 and 255) followed by a
+    BC1 colour block read in four-colour mode.  blocks [by, bx, 16] uint8 -> RGBA8 [height, width, 4].  All blocks at once."""
+    by, bx = blocks.shape[:2]
+    out = bc1_decode_blocks(blocks[..., 8:], bx * 4, by * 4, four_colour_always=True).copy()
+    b = blocks[..., :8].astype(np.int64)
+    a0, a1 = b[..., 0:1], b[..., 1:2]; j = np.arange(8)
+    six = ((8 - j) * a0 + (j - 1) * a1) // 7
+    four = np.where(j == 6, 0, np.where(j == 7, 255, ((6 - j) * a0 + (j - 1) * a1) // 5))
+    pal = np.where(j == 0, a0, np.where(j == 1, a1, np.where(a0 > a1, six, four)))                                                      # [by, bx, 8]
+    bits = sum(b[..., 2 + k] << (8 * k) for k in range(6))
+    sel = (bits[..., None] >> (3 * np.arange(16))) & 7
+    out[..., 3] = _raster_blocks(np.take_along_axis(pal, sel, -1)[..., None], bx * 4, by * 4)[..., 0]
+    return out[:height, :width]
+
+
+def bc1_decode_blocks_scalar(blocks, width, height, four_colour_always=False):
+    """Block-at-a-time form of bc1_decode_blocks (the original statement; tests/test_hipemu_transcode_ref.py holds the two equal on random blocks).
+    Independent BC1 (DXT1) colour-block decoder written from the format description: colour0 / colour1 as little-endian RGB565, 16 2-bit
     indices in raster order from bit 0; colour0 > colour1 (or four_colour_always, as inside BC2 / BC3): palette c0, c1, (2 c0 + c1) / 3,
     (c0 + 2 c1) / 3; otherwise c0, c1, (c0 + c1) / 2 and transparent black.  blocks [by, bx, 8] uint8 -> RGBA8 [height, width, 4]."""
     by, bx = blocks.shape[:2]
@@ -195,12 +240,12 @@ def bc1_decode_blocks(blocks, width, height, four_colour_always=False):
     return out[:height, :width]
 
 
-def bc3_decode_blocks(blocks, width, height):
-    """Independent BC3 (DXT5) decoder: a BC4 alpha block (alpha0, alpha1, 16 3-bit indices in raster order from bit 0; alpha0 > alpha1: six
+def bc3_decode_blocks_scalar(blocks, width, height):
+    """Block-at-a-time form of bc3_decode_blocks.  Independent BC3 (DXT5) decoder: a BC4 alpha block (alpha0, alpha1, 16 3-bit indices in raster order from bit 0; alpha0 > alpha1: six
     interpolated values ((8 - j) a0 + (j - 1) a1) / 7 for index j = 2 .. 7, else four interpolated values, then 0 and 255) followed by a
     BC1 colour block read in four-colour mode.  blocks [by, bx, 16] uint8 -> RGBA8 [height, width, 4]."""
     by, bx = blocks.shape[:2]
-    out = bc1_decode_blocks(blocks[..., 8:], by * 4, bx * 4, four_colour_always=True).copy()
+    out = bc1_decode_blocks_scalar(blocks[..., 8:], bx * 4, by * 4, four_colour_always=True).copy()      # (width, height: was swapped, harmless on the square grids it had seen)
     for y in range(by):
         for x in range(bx):
             b = [int(v) for v in blocks[y, x, :8]]

@@ -350,6 +350,10 @@ def test_gpu_uastc_mode_bit_exact(oracle):
             nl, by, bx = astc.shape[:3]
             img = px.reshape(nl, by, bx, 4, 4, 4).transpose(0, 1, 3, 2, 4, 5).reshape(nl, by * 4, bx * 4, 4)[:, :dec.shape[1], :dec.shape[2]]
             assert np.array_equal(img, dec), name
+        # UASTC -> BC7 at full size like ASTC: the 2048^2 layer of the block-by-block device cases (tests/test_gpu_transcode_ref.py), same oracle call
+        import transcode_cases as TC
+        big = cd.encode_texture_segment(TC.sequence(1, 2048, 2048, 950, True))
+        assert np.array_equal(cd.transcode_texture_segments_bc7([big])[0], oracle.uastc_ktx2_decode(big, "bc7")), "2048"
         segs = [synth.texture_sequence(2, size=128, seed=s) for s in range(3)]
         assert cd.encode_texture_segments(segs) == [oracle.uastc_ktx2_encode(t) for t in segs]
         with pytest.raises(uvol.UvolError):                                            # ASTC is the target of UASTC sources only

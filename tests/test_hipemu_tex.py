@@ -198,7 +198,9 @@ def _check_alpha_targets(oracle, cd, data, gate_a=38.0, gate_c=32.0):      # (co
         assert psnr_a(g[..., 3], ref[..., 3]) > gate_a and psnr_rgb(g, ref) > gate_c, (l, psnr_a(g[..., 3], ref[..., 3]), psnr_rgb(g, ref))
         # the extreme levels of every alpha block are exact in BC7 (endpoints) - in particular fully transparent / opaque texels stay so
         assert np.array_equal(g[..., 3][ref[..., 3] == 0], ref[..., 3][ref[..., 3] == 0])
-        assert np.all(a[ref[..., 3] == 255] >= 250) or True
+        # (no such statement for EAC: it has no exact endpoints, its search minimises the error summed over the block, so no bound on a single
+        # opaque texel follows from the rule - the line that stood here, `a[opaque] >= 250 or True`, asserted nothing.  What these texels decode to
+        # is pinned block by block, with index optimality and exact solid blocks, in tests/test_hipemu_transcode_ref.py.)
     return e2, b7
 
 

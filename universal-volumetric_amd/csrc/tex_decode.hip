@@ -384,7 +384,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_etc1(TexDecJob *jobs) {
 // levels abase + {-a, -b, +b, +a} (green channel, clamped); EAC alpha is base + multiplier * table[j], eight levels out of 16 tables:
 // every (table, multiplier 1..15) is tried with five base values around the middle of the levels, each level takes its nearest EAC
 // level, the error is summed over the 16 pixels, the first best (table, multiplier, base ascending) wins.  Not a restatement of the
-// basis transcoder's table-driven path (its tables are not in the reference): gated by alpha PSNR against the RGBA32 decode.
+// basis transcoder's table-driven path (its tables are not in the reference): gated by alpha PSNR against the RGBA32 decode and checked
+// block by block against the plain reference of this rule in tests/transcode_ref.py.
 // Alpha block bytes: base, multiplier << 4 | table, then 16 x 3-bit indices, pixel i = 4 * x + y, first pixel in the top bits.
 __device__ const int8_t EAC_MOD[16][8] = {
   { -3, -6, -9, -15, 2, 5, 8, 14 }, { -3, -7, -10, -13, 2, 6, 9, 12 }, { -2, -5, -8, -13, 1, 4, 7, 12 }, { -2, -4, -6, -13, 1, 3, 5, 12 },
@@ -441,14 +442,17 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_etc2a(TexDecJob *jobs) {
 }
 
 // ---- K3'c: BC1 / BC3 targets (round 5; the stock loader's `dxtSupported` row, src/lib/KTX2Loader.js:610-618: TranscoderFormat.BC1 for an
-// opaque file, BC3 for one with alpha slices - its choice where neither BPTC nor ETC2 exists).  Colour: the block's darkest / brightest ETC1S
-// colour rounded to RGB565 are the endpoints of a four-colour BC1 block (palette c0, c1, (2 c0 + c1) / 3, (c0 + 2 c1) / 3: ETC1's inner
+// opaque file, BC3 for one with alpha slices - its choice where neither BPTC nor ETC2 exists).  Colour: the darkest / brightest ETC1S
+// colour the block's selectors USE, rounded to RGB565, are the endpoints of a four-colour BC1 block (palette c0, c1, (2 c0 + c1) / 3, (c0 + 2 c1) / 3: ETC1's inner
 // colours sit at 0.31 - 0.39 of the span, BC1's at 1/3); each of the four ETC1S colours takes the palette entry nearest in squared error
 // (clamping can bend the line), pixels follow their selectors.  An opaque BC1 block needs colour0 > colour1 as 16-bit numbers (otherwise
-// index 3 means transparent black): endpoints are swapped and indices remapped where needed, equal endpoints use index 0 only.  BC3 = a BC4
+// index 3 means transparent black): endpoints are swapped and indices remapped where needed, equal endpoints use index 0 only.  For an
+// ETC1S source the brightest used colour is >= the darkest in every channel, so colour0 >= colour1 and the swap never runs (all 32^3 x 8
+// endpoints x 10 selector ranges enumerated: tests/test_hipemu_transcode_ref.py); equal endpoints happen (a block of one selector).  BC3 = a BC4
 // alpha block (alpha0 = highest, alpha1 = lowest level the block uses, eight-value mode, every level on its nearest palette value; equal
 // levels: index 0) followed by the same colour block, which BC3 always reads in four-colour mode.  Re-fits, not restatements of the basis
-// transcoder's tables (not in the reference): gated by PSNR against the RGBA32 decode through an independent decoder (tests/helpers.py).
+// transcoder's tables (not in the reference): gated by PSNR against the RGBA32 decode through an independent decoder (tests/helpers.py)
+// and checked block by block against the plain reference of this rule in tests/transcode_ref.py (palette entries ascending, first best).
 // Layouts: colour0, colour1 (u16 LE, R in the top 5 bits), 16 x 2-bit indices raster order from bit 0; alpha0, alpha1, 16 x 3-bit indices.
 template <bool BC3>
 __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc13(TexDecJob *jobs) {
@@ -488,9 +492,13 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc13(TexDecJob *jobs) {
     const int base = (e[c] << 3) | (e[c] >> 2);
     for (int k = 0; k < 4; k++) { const int v = base + MODS[e[3] & 7][k]; col[k][c] = v < 0 ? 0 : (v > 255 ? 255 : v); }
   }
-  // endpoints: brightest -> colour0, darkest -> colour1, rounded to 5 / 6 / 5 bits
-  const int q0[3] = { (col[3][0] * 31 + 127) / 255, (col[3][1] * 63 + 127) / 255, (col[3][2] * 31 + 127) / 255 };
-  const int q1[3] = { (col[0][0] * 31 + 127) / 255, (col[0][1] * 63 + 127) / 255, (col[0][2] * 31 + 127) / 255 };
+  // endpoints: brightest colour the block uses -> colour0, darkest -> colour1, rounded to 5 / 6 / 5 bits
+  uint32_t cused = 0; for (int i = 0; i < 16; i++) cused |= 1u << ((sel >> (2 * i)) & 3u);
+  int klo = 0, khi = 3;
+  while (!((cused >> klo) & 1u)) klo++;
+  while (!((cused >> khi) & 1u)) khi--;
+  const int q0[3] = { (col[khi][0] * 31 + 127) / 255, (col[khi][1] * 63 + 127) / 255, (col[khi][2] * 31 + 127) / 255 };
+  const int q1[3] = { (col[klo][0] * 31 + 127) / 255, (col[klo][1] * 63 + 127) / 255, (col[klo][2] * 31 + 127) / 255 };
   uint32_t c0 = (uint32_t)((q0[0] << 11) | (q0[1] << 5) | q0[2]), c1 = (uint32_t)((q1[0] << 11) | (q1[1] << 5) | q1[2]);
   int pal[4][3];
   { const int e0[3] = { (q0[0] << 3) | (q0[0] >> 2), (q0[1] << 2) | (q0[1] >> 4), (q0[2] << 3) | (q0[2] >> 2) };
@@ -515,12 +523,14 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc13(TexDecJob *jobs) {
 
 // ---- K3'': BC7 target (what KTX2Loader picks on desktop GPUs, reference src/lib/KTX2Loader.js:591-689: astc, then bptc).  An ETC1S
 // block has four colours base + {-a, -b, +b, +a}, clamped per channel.  Two single-subset BC7 modes can hold them with the
-// darkest / brightest colour as endpoints: mode 5 (7-bit RGB endpoints widened by bit replication, 2-bit indices, weights
+// darkest / brightest colour the block's selectors USE as endpoints (col[lowest used selector] >> 1, col[highest used selector] >> 1: a
+// block of one selector has equal endpoints and decodes to one colour within 1): mode 5 (7-bit RGB endpoints widened by bit replication, 2-bit indices, weights
 // 0/21/43/64 - close to ETC1's inner colours at ~0.35 of the span, and exact for black and white; separate 8-bit alpha = 255)
 // and mode 6 (7-bit endpoints + p-bit, 4-bit indices; opaque alpha forces both p-bits to 1, so endpoints are odd values).
 // Each of the four colours takes the index closest in squared error over the three channels (clamping can bend the line,
-// hence the search); the block keeps the mode with the smaller error summed over its 16 pixels (ties: mode 5).  Not a
-// restatement of the basis transcoder's table-driven mode-5 path: the gate for this target is PSNR against the RGBA32 decode.
+// hence the search; indices ascending, the first best wins); the block keeps the mode with the smaller error summed over its 16
+// pixels (ties: mode 5).  Not a restatement of the basis transcoder's table-driven mode-5 path: the gate for this target is PSNR
+// against the RGBA32 decode, and every block is checked against the plain reference of this rule in tests/transcode_ref.py.
 // Bit layouts, LSB first.  Mode 5: 6 bits (1 << 5); rotation 2 (= 0); R0 R1 G0 G1 B0 B1, 7 bits each; A0 A1, 8 bits each;
 // colour indices 1 + 15 * 2 bits; alpha indices 1 + 15 * 2 bits (all 0).  Mode 6: 7 bits (1 << 6); R0 R1 G0 G1 B0 B1 A0 A1,
 // 7 bits each; P0 P1; indices 3 + 15 * 4 bits.  Pixel 0's index has its MSB implied 0: otherwise swap the endpoints and
@@ -539,10 +549,13 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc7(TexDecJob *jobs) {
   for (int c = 0; c < 3; c++) {
     const int base = (e[c] << 3) | (e[c] >> 2);
     for (int k = 0; k < 4; k++) { const int v = base + MODS[e[3] & 7][k]; col[k][c] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-    lo7[c] = col[0][c] >> 1; hi7[c] = col[3][c] >> 1;
   }
   uint32_t hist[4] = { 0, 0, 0, 0 };
   for (int i = 0; i < 16; i++) hist[(sel >> (2 * i)) & 3u]++;
+  int klo = 0, khi = 3;                                  // the darkest / brightest colour the block USES (a solid block: one colour, equal endpoints)
+  while (!hist[klo]) klo++;
+  while (!hist[khi]) khi--;
+  for (int c = 0; c < 3; c++) { lo7[c] = col[klo][c] >> 1; hi7[c] = col[khi][c] >> 1; }
   uint32_t idx5[4], idx6[4], err5 = 0, err6 = 0;
   for (int k = 0; k < 4; k++) {
     uint32_t b5 = 0, e5 = 0xffffffffu, b6 = 0, e6 = 0xffffffffu;
@@ -562,14 +575,18 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc7(TexDecJob *jobs) {
   auto put = [&](unsigned long long v, int n) { if (pos < 64) { lo |= v << pos; if (pos + n > 64) hi |= v >> (64 - pos); } else hi |= v << (pos - 64); pos += n; };
   // A file with alpha slices (what the stock loader asks BC7 with alpha for, src/lib/KTX2Loader.js:672-676): always mode 5, whose alpha has
   // its own 8-bit endpoints and 2-bit indices.  The alpha block's four levels (green channel of the alpha slice, as the basis transcoder
-  // takes them) give the endpoints (lowest / highest level, exact) and every level the nearest of the four interpolated values.
+  // takes them) give the endpoints (lowest / highest level the block uses, exact) and every level the first nearest of the four interpolated values.
   uint32_t aidx[4] = { 0, 0, 0, 0 }, asel = 0; int a_lo = 255, a_hi = 255;
   if (J.ashift) {
     const size_t oa = o + (size_t)J.bx * J.by;
     const uint8_t *ae = J.endpoints + 4 * (size_t)J.ei[oa]; asel = J.selectors[J.si[oa]];
     int al[4];
     for (int k = 0; k < 4; k++) { const int v = ((ae[1] << 3) | (ae[1] >> 2)) + MODS[ae[3] & 7][k]; al[k] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-    a_lo = al[0]; a_hi = al[3];
+    uint32_t aused = 0; for (int i = 0; i < 16; i++) aused |= 1u << ((asel >> (2 * i)) & 3u);
+    int alo = 0, ahi = 3;
+    while (!((aused >> alo) & 1u)) alo++;
+    while (!((aused >> ahi) & 1u)) ahi--;
+    a_lo = al[alo]; a_hi = al[ahi];
     for (int k = 0; k < 4; k++) { uint32_t bw = 0; int be = 1 << 30; for (uint32_t w = 0; w < 4; w++) { const int d = ((a_lo * (64 - W2[w]) + a_hi * W2[w] + 32) >> 6) - al[k]; if (d * d < be) { be = d * d; bw = w; } } aidx[k] = bw; }
   }
   if (err5 <= err6 || J.ashift) {

@@ -546,7 +546,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_uastc_decode(UastcJob *jobs, con
     // ETC1 fit, not the basis transcoder's hint-driven one (its tables are not in the reference): both flips are tried; a half-block's base is its
     // mean colour, in differential mode (5 bits + a 3-bit delta clamped to [-4, 3], which also keeps the block out of ETC2's T / H / planar modes)
     // when both deltas fit, else in individual mode (4 bits each); per half-block the intensity table with the smallest error under per-texel
-    // optimal modifiers; the flip with the smaller total error wins (ties: flip 0).  Gated by PSNR against the RGBA32 decode.
+    // optimal modifiers; the flip with the smaller total error wins (ties: flip 0; tables and modifiers ascending, first best).  Gated by PSNR against the RGBA32
+    // decode and checked block by block against the plain reference of this rule in tests/transcode_ref.py.
     const int MAG[8][2] = { { 2, 8 }, { 5, 17 }, { 9, 29 }, { 13, 42 }, { 18, 60 }, { 24, 80 }, { 33, 106 }, { 47, 183 } };
     uint8_t *out = J.out[l] + (target == 6 ? 16 : 8) * (size_t)b;
     if (target == 6) {
@@ -616,7 +617,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_uastc_decode(UastcJob *jobs, con
     // src/lib/KTX2Loader.js:610-618).  Colour: range fit - the corners of the texels' bounding box, the R and B ends swapped where the channel
     // runs against G (sign of the covariance), pulled in by 1/16 of the range, rounded to RGB565; every texel takes the nearest of the four
     // palette colours; an opaque BC1 block needs colour0 > colour1 (swap + remap, equal endpoints: index 0).  Alpha (BC3): a BC4 block with
-    // alpha0 = the largest, alpha1 = the smallest alpha of the block, eight-value mode.  Re-fits gated by PSNR against the RGBA32 decode.
+    // alpha0 = the largest, alpha1 = the smallest alpha of the block, eight-value mode.  Re-fits gated by PSNR against the RGBA32 decode and
+    // checked block by block against the plain references of these rules in tests/transcode_ref.py.
     uint8_t *out = J.out[l] + (target == 4 ? 16 : 8) * (size_t)b;
     if (target == 4) {
       int a0 = 0, a1 = 255;
