@@ -360,6 +360,48 @@ int uvol_decode_mesh_batch_dev(uvol_ctx *ctx, const uint8_t *const *drc, const s
 int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                uvol_decoded_mesh *out, uint8_t *const *face_material, int *has_material, int *status);
 
+/* ---- render-ready form of the geometry decode (additive: uvol_abi_version stays 1) ----
+ * What the stock player obtains from its loader (reference src/lib/DRACOLoader.js:470-569: decodeGeometry / decodeIndex / decodeAttribute)
+ * is ONE vertex array per attribute, all of num_points entries, plus one uint32 index per corner, which go straight into a BufferGeometry.
+ * uvol_decode_mesh_batch hands back the inverse of uvol_mesh instead - a value count and an index stream per attribute -, which no
+ * graphics API draws.  This entry point welds the three streams on the device (csrc/geo_weld.hpp):
+ *   point    = a distinct tuple (idx_pos[c], idx_uv[c], idx_nrm[c]) over the corners c = 0 .. 3 * n_faces - 1, in exactly the face and corner
+ *              order uvol_decode_mesh_batch returns; an attribute the file does not carry is left out of the tuple;
+ *   numbering: points are numbered by FIRST APPEARANCE in that corner order - deterministic, and vertex order stays coherent with face
+ *              order.  It is not Draco's own point numbering, which nothing at hand pins down (the recorded .drc files carry no point
+ *              ids and the reference holds no decoder to run);
+ *   values   : index[c] is the point of corner c; the values of point p are the bit-identical floats uvol_decode_mesh_batch produces for the
+ *              entries of p's tuple (the weld adds no arithmetic).
+ * Layouts: UVOL_POINTS_PLANAR - pos / uv / nrm receive 3 / 2 / 3 floats per point (any may be NULL to skip that output; the array of an
+ * absent attribute is left alone); UVOL_POINTS_INTERLEAVED - `pos` is the one buffer, 32 bytes per point = pos[3] nrm[3]
+ * uv[2], uv / nrm are ignored, the slot of an absent attribute is written as zeros.  has_uv / has_nrm say which attributes the file carries.
+ * A DEVICE interleaved buffer must be 16-byte aligned (the kernels write it with 16-byte stores); host outputs are copied and need no
+ * alignment.  An unknown layout or a misaligned device buffer in any frame is a mistake of the caller, not of a file: the whole call returns
+ * UVOL_E_INVALID and nothing is decoded.
+ * Capacity: n_points <= 3 * n_faces, so uvol_drc_info's max_values always suffices as cap_points.  Frames fail alone, status[i] (may be NULL:
+ * the worst code is then the return value): a frame whose points exceed cap_points, or whose faces exceed cap_faces, gets UVOL_E_NOSPACE
+ * with n_points / n_faces set to the count it needs and none of its arrays written; a foreign file (uvol_drc_info refuses it) UVOL_E_INVALID;
+ * a corrupt one UVOL_E_ENCODE; one with a position entry shared by more than 4096 corners UVOL_E_UNSUPPORTED (every corner compares itself
+ * against the corners of its position entry).  Sequential files (`-cl 0`) go through the same entry and come out under the same numbering.
+ * Output memory as in the existing decode: device pointers when outputs_on_device (written in place by the weld kernels, no copy);
+ * pageable host arrays through the pinned double buffers; arrays that ALL lie in uvol_host_alloc memory written by DMA where they are.
+ * Out of scope: material ids on this form (use uvol_decode_mesh_batch_mat: its face order is the same); quantised or half-float vertex
+ * formats.  uvol_decode_mesh_batch, _dev and _mat are unchanged: they launch none of the weld kernels and carve none of their scratch. */
+enum { UVOL_POINTS_PLANAR = 0, UVOL_POINTS_INTERLEAVED = 1 };
+typedef struct uvol_decoded_points {
+  /* in */
+  uint32_t cap_faces;              /* index holds 3 * cap_faces entries */
+  size_t cap_points;               /* planar: pos / nrm hold 3 * cap_points floats, uv 2 * cap_points; interleaved: pos holds 8 * cap_points */
+  uint32_t layout;                 /* UVOL_POINTS_PLANAR / UVOL_POINTS_INTERLEAVED */
+  float *pos, *uv, *nrm;
+  uint32_t *index;                 /* may be NULL */
+  /* out */
+  uint32_t n_faces, n_points;
+  uint32_t has_uv, has_nrm;
+} uvol_decoded_points;
+int uvol_decode_mesh_batch_points(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
+                                  uvol_decoded_points *out, int *status);
+
 /* ---- measurement hooks (bench.py / rocprof cross-check) ---- */
 /* When enabled, every kernel group is bracketed by hipEvents on the ctx stream. */
 int uvol_profile_enable(uvol_ctx *ctx, int on);

@@ -42,6 +42,13 @@ mat_streams = MC.run_values(o, cd); MC.run_shuffled(o, cd); MC.run_refusal(o, cd
 MC.run_decoder(o, cd, MC.HostMem(), mat_streams[:2])
 with tempfile.TemporaryDirectory() as td:
     MC.run_ingest(o, cd, MC.HostMem(), pathlib.Path(td))
+# render-ready decode (tests/test_hipemu_points.py's checks): the weld kernels' counters, fans and scans, the staged and the in-place outputs,
+# frames that fail alone (truncated, foreign, one point / one face short), sequential streams, two recorded files
+import points_cases as PC
+c0p = uvol.Codec(lib_path=lib, DRACO_COMPRESSION_LEVEL=0)
+PC.run_subsets(o, cd, c0p); PC.run_ragged(o, cd, c0p); PC.run_long_fan(o, cd, c0p); PC.run_memory_forms(o, cd, c0p, MC.HostMem(), lib_path=lib)
+PC.run_recorded(o, cd, [open(os.path.join(ROOT, "tests", "golden", n), "rb").read() for n in ("00000.drc", "00075.drc")])
+c0p.close()
 # corrupted decoder inputs: bit flips, truncations, overwritten words - a clean error or a decoded result, never an out-of-bounds access
 rng = np.random.default_rng(5)
 outcomes = {}

@@ -30,6 +30,7 @@ __device__ inline uint32_t block_sum(uint32_t v) {
   return r;
 }
 
+#ifndef GEO_SCAN_BLOCK_ONLY      // (geom_decode.hip takes the block-level scans above for its weld stage, geo_weld.hpp; the kernels below read the encoder's GeoJob)
 // scan selectors.  The producers of the KEEP / ELIG / EVENTS flags write the per-block sums themselves (block_sum), so only
 // SCAN_ORI still runs k_scan_blocks; k_scan_sums turns the sums into block offsets for all four.
 enum { SCAN_KEEP = 0, SCAN_ELIG = 1, SCAN_ORI = 2, SCAN_EVENTS = 3, SCAN_SEQ = 4 };      // SCAN_SEQ: per input corner (sequential connectivity)
@@ -71,3 +72,4 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_scan_sums(GeoJob *jobs, int sel)
 // Corners per thread in the per-corner gather kernels (k_edge_match, k_aseg_a/b): they are latency-bound at full occupancy, so a
 // thread issues every level of its dependent loads for GEO_ILP corners (one block stride apart: coalesced) before using any.
 #define GEO_ILP 4
+#endif      // GEO_SCAN_BLOCK_ONLY

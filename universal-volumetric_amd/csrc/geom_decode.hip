@@ -14,6 +14,7 @@
 //   k_gdec_rans     again for the attribute symbol streams (their lengths are the traversal results)
 //   k_gdec_pred     1 lane / (decoder, frame)   parallelogram / tex-coord-portable / geometric-normal prediction + transforms
 //   k_gdec_finish   parallel           dequantisation (fp32, octahedral) and per-corner entry indices
+//   k_weld_*        parallel           uvol_decode_mesh_batch_points only (geo_weld.hpp): one index per corner + one value record per point
 #include "uvol_common.hpp"
 #include "geom_device.hpp"
 #include "uvol_ws.hpp"
@@ -34,6 +35,12 @@ struct GDAtt {
   int32_t table;                 // 0 = base corner table, 1 + i = attribute table i
   int32_t *vals;                 // ne * nc decoded integers, entry order
   GDRabs aux;                    // uv orientation bits / normal flip bits
+};
+// weld stage (geo_weld.hpp; uvol_decode_mesh_batch_points): scratch, outputs and results of one frame; all zero for the other entry points
+struct GDWeldJob {
+  uint32_t on, layout, cap, np;        // layout: UVOL_POINTS_*; cap: points the value outputs hold; np: points of the frame (out)
+  uint32_t *cnt, *fan, *rep, *pid, *bsum_p, *bsum_c;
+  float *o_val[3]; uint32_t *o_index;  // planar: pos / uv / nrm (any may be null); interleaved: o_val[0] is the one buffer
 };
 struct GeoDecJob {
   const uint8_t *file; uint32_t file_len; int32_t status;
@@ -56,6 +63,7 @@ struct GeoDecJob {
   uint8_t *uvgeo;                // GDUvGeo per tex-coord entry
   // outputs (device): position / uv / normal values and per-corner entry indices
   float *o_val[3]; uint32_t *o_idx[3]; uint32_t o_n[3]; int32_t o_dec[3];
+  GDWeldJob w;
   uint8_t *o_mat; int32_t o_has_mat;      // material id per face (the face order of o_idx), when the file carries a GENERIC uint8 1-component vertex attribute
 };
 
@@ -1005,6 +1013,10 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_facemat(GeoDecJob *jobs, Ge
   J.o_mat[f] = (uint8_t)J.att[d].vals[G.v2d[0][J.c2v[3 * (size_t)f]]];
 }
 
+#define GEO_SCAN_BLOCK_ONLY
+#include "geo_scan.hpp"
+#include "geo_weld.hpp"
+
 // ================================================================================================
 // host side
 // ================================================================================================
@@ -1062,8 +1074,12 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_clear(GeoDecJob *jobs) {
 // arrays (traversal order, predictor scratch, symbols, values) are sized for `ecap` entries - faces + faces / 2 in the compact
 // layout, a frame that needs more (every corner its own entry) fails with GD_E_WS_OVERFLOW on the device and is decoded again
 // with the worst case (3 x faces).  265 -> ~90 MB per 200 k-face frame.
-enum { DS_INDEX = 0, DS_CTX, DS_CONN, DS_TABLES, DS_TRAV, DS_SYM, DS_PRED, DS_FIN, DS_COUNT };
-static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool full, GDPlan &P) {
+// weld: 0 none (every entry point but uvol_decode_mesh_batch_points: nothing of the weld is carved), 1 scratch, 2 scratch + staging of the
+// outputs (host outputs).  The weld runs when everything else is dead - its inputs, the arrays k_gdec_finish wrote, lie in the output area -,
+// so its arrays share the addresses of the predictors' and the frame's peak does not grow.
+enum { DS_INDEX = 0, DS_CTX, DS_CONN, DS_TABLES, DS_TRAV, DS_SYM, DS_PRED, DS_FIN, DS_WELD, DS_COUNT };
+struct GDWeldStage { uint32_t *index; uint8_t *vals; };
+static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool full, GDPlan &P, int weld = 0, GDWeldStage *stage = nullptr) {
   const size_t nf = (size_t)J.nf, nc = 3 * nf, maxv = (size_t)J.nev + nf + 8;          // nsplit <= nf
   const size_t E = full ? nc + 3 : std::min(nc + 3, nf + nf / 2 + 4096);
   J.ecap = (uint32_t)E;
@@ -1087,10 +1103,17 @@ static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool f
   }
   for (int k = 1; k < 4; k++) DCARVE(G.rec[k], (r8 ? 32 : 64) * (nf + 1), DS_TRAV, DS_TRAV);     // 8- or 16-byte corner records, decided per batch (geo_records8)
   for (int k = 0; k < 3; k++) { DCARVE(G.order[k], 4 * (E + 3), DS_TRAV, DS_FIN); DCARVE(G.v2d[k], 4 * (std::max(E, maxv) + 3), DS_TRAV, DS_FIN); DCARVE(G.t_stack[k], 4 * (nf + 2), DS_TRAV, DS_TRAV); DCARVE(G.t_vvis[k], std::max(E, maxv) / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); DCARVE(G.t_fvis[k], nf / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); }
+  GDWeldStage stg{ nullptr, nullptr };
+  if (weld) {
+    DCARVE(J.w.cnt, 4 * (E + 2), DS_WELD, DS_WELD); DCARVE(J.w.fan, 4 * nc, DS_WELD, DS_WELD); DCARVE(J.w.rep, 4 * nc, DS_WELD, DS_WELD); DCARVE(J.w.pid, 4 * nc, DS_WELD, DS_WELD);
+    DCARVE(J.w.bsum_p, 4 * (E / UVOL_BLOCK + 4), DS_WELD, DS_WELD); DCARVE(J.w.bsum_c, 4 * (nc / UVOL_BLOCK + 4), DS_WELD, DS_WELD);
+    if (weld == 2) { DCARVE(stg.index, 4 * nc, DS_WELD, DS_WELD); DCARVE(stg.vals, 32 * nc, DS_WELD, DS_WELD); }      // (n_points <= corners)
+  }
 #undef DCARVE
-  const std::vector<uint64_t> key = { (uint64_t)nf, (uint64_t)J.nev, (uint64_t)r8 | ((uint64_t)full << 1), (uint64_t)items.size() };
+  const std::vector<uint64_t> key = { (uint64_t)nf, (uint64_t)J.nev, (uint64_t)r8 | ((uint64_t)full << 1) | ((uint64_t)weld << 2), (uint64_t)items.size() };
   if (key != P.key) { P.total = uvol_ws_place(items, &P.zero, DS_COUNT, "geometry decode"); P.offs.resize(items.size()); for (size_t i = 0; i < items.size(); i++) P.offs[i] = items[i].off; P.key = key; }
   for (size_t i = 0; i < slots.size(); i++) *slots[i] = base ? (void *)(base + P.offs[i]) : nullptr;
+  if (stage) *stage = stg;
   J.ws_base = base; J.ws_zero = P.zero;
   G.status = 0; G.nf = (uint32_t)nf; G.nc = (uint32_t)nc; G.nad = 2; G.nverts = 0xffffffffu; G.ecap = (uint32_t)E;
   G.nopp = J.opp; G.bvert = J.c2v; G.avert[0] = J.t_c2v[0]; G.avert[1] = J.t_c2v[1]; G.seam[0] = J.edge_seam[0]; G.seam[1] = J.edge_seam[1];
@@ -1098,15 +1121,28 @@ static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool f
   return P.total;
 }
 
+// pts: uvol_decode_mesh_batch_points (the weld stage runs and fills pts[i]; `out` then only carries capacities, its arrays are null)
 static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev,
-                                 uint8_t *const *fmat = nullptr, int *has_mat = nullptr);
+                                 uint8_t *const *fmat = nullptr, int *has_mat = nullptr, uvol_decoded_points *pts = nullptr);
 int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool outputs_on_device,
                      uint8_t *const *face_material, int *has_material) {
   return geo_decode_batch_impl(ctx, files, lens, n, out, status, false, outputs_on_device, face_material, has_material);
 }
+// every file is a .drc by its header (the entry point sorted the others out); frames fail alone: UVOL_E_NOSPACE with n_points = the count
+// the frame needs, UVOL_E_UNSUPPORTED for a position entry shared by more than GW_MAXFAN corners, UVOL_E_ENCODE for a corrupt file
+int geo_decode_points(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_points *pts, int *status, bool outputs_on_device) {
+  std::vector<uvol_decoded_mesh> meshes((size_t)(n > 0 ? n : 0), uvol_decoded_mesh{});
+  for (int i = 0; i < n; i++) {
+    uint32_t nev = 0, nf = 0;
+    if (!gdec_header(files[i], lens[i], &nev, &nf)) { ctx->set_error("frame %d: not a Draco 2.2 mesh", i); return UVOL_E_INVALID; }
+    meshes[(size_t)i].cap_faces = nf; meshes[(size_t)i].cap_values = 3 * (size_t)nf;
+  }
+  return geo_decode_batch_impl(ctx, files, lens, n, meshes.data(), status, false, outputs_on_device, nullptr, nullptr, pts);
+}
 static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev,
-                                 uint8_t *const *fmat, int *has_mat) {
+                                 uint8_t *const *fmat, int *has_mat, uvol_decoded_points *pts) {
   const bool want_mat = fmat != nullptr || has_mat != nullptr;
+  const int weld = pts ? (out_dev ? 1 : 2) : 0;
   GeoDecState *T = ctx->geodec;
   if (n <= 0) return UVOL_OK;
   T->hjobs.assign((size_t)n, GeoDecJob{}); T->hg.assign((size_t)n, GeoJob{});
@@ -1122,7 +1158,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GeoDecJob &J = T->hjobs[i]; J.nf = (int32_t)nf; J.nev = (int32_t)nev; J.file_len = (uint32_t)lens[i];
     max_nf = std::max(max_nf, nf); max_nev = std::max(max_nev, nev);
     foff[i] = ftot; ftot += a256(lens[i] + 16);
-    GeoJob gtmp{}; const size_t w = gdec_carve(J, gtmp, nullptr, r8, full, T->plan);
+    GeoJob gtmp{}; const size_t w = gdec_carve(J, gtmp, nullptr, r8, full, T->plan, weld);
     woff[i] = wtot; wtot += a256(w);
     { const size_t nc = 3 * (size_t)nf; ooff[i] = otot; otot += 3 * (a256(4 * 3 * nc) + a256(4 * nc)) + (want_mat ? a256(nf) : 0); }
   }
@@ -1138,8 +1174,17 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     uint8_t *fd = (uint8_t *)T->files.p + foff[i];
     ups.push_back(UvolUpItem{ foff[i], files[i], lens[i] });      // one staged upload for the whole call below (1920 pageable copies cost ~0.1 s)
     J.file = fd; J.status = 0;
-    (void)gdec_carve(J, G, (uint8_t *)T->slab.p + woff[i], r8, full, T->plan);
+    GDWeldStage stg{ nullptr, nullptr };
+    (void)gdec_carve(J, G, (uint8_t *)T->slab.p + woff[i], r8, full, T->plan, weld, &stg);
     const size_t nc = 3 * (size_t)J.nf;
+    if (pts) {                                                               // device outputs are written where the caller wants them; host outputs are staged in the workspace
+      const uvol_decoded_points &P = pts[i]; GDWeldJob &W = J.w;
+      W.on = 1; W.layout = P.layout; W.cap = (uint32_t)std::min(P.cap_points, nc); W.np = 0;
+      W.o_index = !P.index ? nullptr : (out_dev ? P.index : stg.index);
+      float *sv = (float *)stg.vals;
+      if (P.layout == UVOL_POINTS_INTERLEAVED) { W.o_val[0] = !P.pos ? nullptr : (out_dev ? P.pos : sv); W.o_val[1] = W.o_val[2] = nullptr; }
+      else { W.o_val[0] = !P.pos ? nullptr : (out_dev ? P.pos : sv); W.o_val[1] = !P.uv ? nullptr : (out_dev ? P.uv : sv + 6 * nc); W.o_val[2] = !P.nrm ? nullptr : (out_dev ? P.nrm : sv + 3 * nc); }
+    }
     uint8_t *ob = (uint8_t *)T->outs.p + ooff[i]; size_t oo = 0;
     for (int k = 0; k < 3; k++) { J.o_val[k] = (float *)(ob + oo); oo += a256(4 * 3 * nc); J.o_idx[k] = (uint32_t *)(ob + oo); oo += a256(4 * nc); }
     J.o_mat = want_mat ? ob + oo : nullptr; J.o_has_mat = 0;
@@ -1196,6 +1241,16 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GLAUNCH(k_gdec_pred, dim3(N, GD_MAXDEC), dim3(64), 0, dj, gj, 1); }
   { uvol_ctx::Scope sc(ctx, "geodec.k8_finish", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj);
     if (want_mat) GLAUNCH(k_gdec_facemat, dim3(uvol_blocks(max_nf), N), dim3(UVOL_BLOCK), 0, dj, gj); }
+  if (pts) { uvol_ctx::Scope sc(ctx, "geodec.k9_weld", 0);
+    const unsigned bp = uvol_blocks((size_t)3 * max_nf + 4);                 // position entries <= ecap <= corners + 3
+    GLAUNCH(k_weld_clear, dim3(bp, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_weld_count, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_weld_scan, dim3(bp, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_weld_sums, dim3(1, N), dim3(UVOL_BLOCK), 0, dj, 0);
+    GLAUNCH(k_weld_scatter, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_weld_rep, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_weld_sums, dim3(1, N), dim3(UVOL_BLOCK), 0, dj, 1);
+    GLAUNCH(k_weld_write, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj); }
   UVOL_HIP_CHECK(ctx, hipGetLastError());
   UVOL_HIP_CHECK(ctx, hipMemcpyAsync(T->hjobs.data(), dj, sizeof(GeoDecJob) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1209,10 +1264,25 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     const GeoDecJob &J = T->hjobs[i]; uvol_decoded_mesh &M = out[i];
     if (has_mat) has_mat[i] = 0;
     if (!full && J.status == GD_E_WS_OVERFLOW) { retry.push_back(i); if (status) status[i] = UVOL_OK; continue; }      // decoded again below, alone, with worst-case sizes
-    const int st = J.status == 0 ? UVOL_OK : UVOL_E_ENCODE;
+    const int st = J.status == 0 ? UVOL_OK : (J.status == GW_E_FAN ? UVOL_E_UNSUPPORTED : UVOL_E_ENCODE);
     if (status) status[i] = st;
     if (st != UVOL_OK) { ctx->set_error("frame %d: corrupt or unsupported .drc (device status %d)", i, J.status); worst = st; continue; }
     M.n_faces = (uint32_t)J.nf;
+    if (pts) {
+      uvol_decoded_points &P = pts[i]; const GDWeldJob &W = J.w; const size_t np = W.np;
+      P.n_faces = (uint32_t)J.nf; P.n_points = W.np; P.has_uv = J.o_n[1] ? 1u : 0u; P.has_nrm = J.o_n[2] ? 1u : 0u;
+      if (W.np > W.cap) { if (status) status[i] = UVOL_E_NOSPACE; worst = UVOL_E_NOSPACE; ctx->set_error("frame %d: %u points, capacity %zu", i, W.np, P.cap_points); continue; }
+      if (!out_dev) {
+        if (P.index) dns.push_back(UvolDnItem{ W.o_index, P.index, (size_t)J.nf * 3 * 4 });
+        if (P.layout == UVOL_POINTS_INTERLEAVED) { if (P.pos) dns.push_back(UvolDnItem{ W.o_val[0], P.pos, 32 * np }); }
+        else {
+          if (P.pos) dns.push_back(UvolDnItem{ W.o_val[0], P.pos, 12 * np });
+          if (P.uv && J.o_n[1]) dns.push_back(UvolDnItem{ W.o_val[1], P.uv, 8 * np });
+          if (P.nrm && J.o_n[2]) dns.push_back(UvolDnItem{ W.o_val[2], P.nrm, 12 * np });
+        }
+      }
+      continue;
+    }
     if (has_mat) has_mat[i] = J.o_has_mat ? 1 : 0;
     if (J.o_has_mat && fmat && fmat[i]) {
       if (out_dev) UVOL_HIP_CHECK(ctx, hipMemcpyAsync(fmat[i], J.o_mat, (size_t)J.nf, hipMemcpyDeviceToDevice, ctx->stream));
@@ -1237,7 +1307,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
   ctx->resolve_profile();
   for (int i : retry) {                                   // frames the compact workspace could not hold (more entries per face than usual)
     int st1 = UVOL_OK;
-    const int rc1 = geo_decode_batch_impl(ctx, files + i, lens + i, 1, out + i, &st1, true, out_dev, fmat ? fmat + i : nullptr, has_mat ? has_mat + i : nullptr);
+    const int rc1 = geo_decode_batch_impl(ctx, files + i, lens + i, 1, out + i, &st1, true, out_dev, fmat ? fmat + i : nullptr, has_mat ? has_mat + i : nullptr, pts ? pts + i : nullptr);
     if (rc1 != UVOL_OK) return rc1;
     if (status) status[i] = st1;
     if (st1 != UVOL_OK) worst = st1;

@@ -20,6 +20,15 @@ class DecodedMesh(C.Structure):
                 ("n_faces", C.c_uint32), ("n_pos", C.c_uint32), ("n_uv", C.c_uint32), ("n_nrm", C.c_uint32)]
 
 
+class DecodedPoints(C.Structure):
+    """uvol_decoded_points: the render-ready form of a decoded frame (one index per corner, one value record per point)."""
+    _fields_ = [("cap_faces", C.c_uint32), ("cap_points", C.c_size_t), ("layout", C.c_uint32), ("pos", C.c_void_p), ("uv", C.c_void_p), ("nrm", C.c_void_p),
+                ("index", C.c_void_p), ("n_faces", C.c_uint32), ("n_points", C.c_uint32), ("has_uv", C.c_uint32), ("has_nrm", C.c_uint32)]
+
+
+UVOL_POINTS_PLANAR, UVOL_POINTS_INTERLEAVED = 0, 1
+
+
 class Params(C.Structure):
     """project-config.json numeric fields used on the hot path (scripts/Encoder.py:171-179)."""
     _fields_ = [("Q_POSITION_ATTR", C.c_int32), ("Q_TEXTURE_ATTR", C.c_int32), ("Q_NORMAL_ATTR", C.c_int32),
@@ -41,7 +50,8 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_ktx2_info", "uvol_decode_texture_segments", "uvol_decode_texture_segments_dev", "uvol_transcode_texture_segments_etc1", "uvol_transcode_texture_segments_bc7", "uvol_transcode_texture_segments_etc2_rgba", "uvol_transcode_texture_segments_astc", "uvol_drc_info", "uvol_decode_mesh_batch", "uvol_profile_enable", "uvol_profile_reset", "uvol_profile_count",
            "uvol_profile_get", "uvol_encode_texture_segments_st", "uvol_transcode_texture_segments_st",
            "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status",
-           "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat"]
+           "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat",
+           "uvol_decode_mesh_batch_points"]
 
 
 def load(path=None):
@@ -67,6 +77,8 @@ def load(path=None):
                                    C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.uvol_decode_mesh_batch_mat.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodedMesh),
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    if hasattr(L, "uvol_decode_mesh_batch_points"):      # (a build that predates the entry point still loads: tools/points_timing.py times one beside this build)
+        L.uvol_decode_mesh_batch_points.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodedPoints), C.POINTER(C.c_int)]
     L.uvol_parse_obj_batch_dev_mat.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.uvol_texture_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_int]; L.uvol_texture_bound.restype = C.c_size_t
     for nm in ("uvol_encode_texture_segment", "uvol_encode_texture_segment_dev"):
@@ -665,6 +677,76 @@ class Codec:
             res.append({k: (cp(a[k][:cnt[k]]) if cnt[k] else None) for k in ("pos", "uv", "nrm")} |
                        {"idx_" + k: (cp(a["idx_" + k][:3 * m.n_faces]) if cnt[k] else None) for k in ("pos", "uv", "nrm")} | {"n_faces": m.n_faces} |
                        ({"face_mat": (cp(fmats[i][:m.n_faces]) if hm[i] else None)} if fmats is not None else {}))
+        return res
+
+    def points_arena_bytes(self, files):
+        """Bytes of a PinnedArena that holds the output arrays of decode_mesh_batch_points(files, arena=...), either layout."""
+        tot = 0
+        for f in files:
+            nf, mv = self.drc_info(f)
+            tot += mv * 32 + 3 * nf * 4 + 4 * 256
+        return tot + 4096
+
+    def decode_mesh_batch_points(self, files, layout="planar", on_device=False, arena=None, raise_on_error=True, metas=None, status_out=None):
+        """files: list of .drc bytes -> per frame the render-ready form (uvol_decode_mesh_batch_points): a dict {index [3*faces] uint32 point per
+        corner, n_faces, n_points, has_uv, has_nrm} plus, layout="planar", pos [n,3] / uv [n,2] / nrm [n,3] float32 (None for an attribute the
+        file does not carry) or, layout="interleaved", points [n,8] float32 = pos[3] nrm[3] uv[2] (absent slots zero).  Points are numbered by
+        first appearance in corner order.  arena (a PinnedArena): the arrays are views into it, written by DMA where they lie.
+        on_device=True: `metas` is a (DecodedPoints * n) array whose pointers are DEVICE memory of the caller (capacities by drc_info); the
+        arrays stay in HBM and the call returns the statuses, the counts are in `metas`.  A failed frame is None (raise_on_error=False); a
+        foreign file or a frame that does not fit fails alone.  status_out (a list): receives the per-frame codes of a host-output call; with
+        `metas` (capacities of the caller's choosing, arrays allocated here) n_points / n_faces of a frame that did not fit are the needed counts."""
+        files = [bytes(f) for f in files]; n = len(files)
+        lay = {"planar": UVOL_POINTS_PLANAR, "interleaved": UVOL_POINTS_INTERLEAVED}[layout]
+        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
+        if on_device:
+            if metas is None:
+                raise UvolError("decode_mesh_batch_points(on_device=True) takes the caller's device buffers in `metas`")
+            for m in metas:
+                m.layout = lay
+            rc = self.L.uvol_decode_mesh_batch_points(self.h, fp, ln, n, 1, metas, st)
+            if rc != UVOL_OK:
+                raise UvolError(f"decode_mesh_batch_points rc={rc}: {self.error()}")
+            return list(st)
+        own = metas is None
+        if own:
+            metas = (DecodedPoints * n)()
+        mk = (lambda shape, dt: arena.take(shape, dt)) if arena is not None else (lambda shape, dt: np.empty(shape, dt))
+        keep = []
+        for i, f in enumerate(files):
+            m = metas[i]; a = {}
+            if own:
+                nf, mv = C.c_uint32(), C.c_uint32()
+                ok = self.L.uvol_drc_info(f, len(f), C.byref(nf), C.byref(mv)) == UVOL_OK      # (a foreign file fails in its own slot below)
+                m.cap_faces = nf.value if ok else 0; m.cap_points = mv.value if ok else 0
+            m.layout = lay
+            cp, cf = max(1, int(m.cap_points)), max(1, int(m.cap_faces))
+            a["index"] = mk((3 * cf,), np.uint32)
+            if lay == UVOL_POINTS_INTERLEAVED:
+                a["points"] = mk((cp, 8), np.float32); m.pos = a["points"].ctypes.data; m.uv = None; m.nrm = None
+            else:
+                a["pos"] = mk((cp, 3), np.float32); a["uv"] = mk((cp, 2), np.float32); a["nrm"] = mk((cp, 3), np.float32)
+                m.pos, m.uv, m.nrm = a["pos"].ctypes.data, a["uv"].ctypes.data, a["nrm"].ctypes.data
+            m.index = a["index"].ctypes.data
+            keep.append(a)
+        rc = self.L.uvol_decode_mesh_batch_points(self.h, fp, ln, n, 0, metas, st)
+        if status_out is not None:
+            status_out[:] = list(st)
+        if rc != UVOL_OK:
+            raise UvolError(f"decode_mesh_batch_points rc={rc}: {self.error()}")
+        res = []
+        for i in range(n):
+            if st[i] != UVOL_OK:
+                if raise_on_error:
+                    raise UvolError(f"frame {i} failed status={st[i]}: {self.error()}")
+                res.append(None); continue
+            m, a = metas[i], keep[i]; npnt = m.n_points
+            r = dict(index=a["index"][:3 * m.n_faces], n_faces=m.n_faces, n_points=npnt, has_uv=bool(m.has_uv), has_nrm=bool(m.has_nrm))
+            if lay == UVOL_POINTS_INTERLEAVED:
+                r["points"] = a["points"][:npnt]
+            else:
+                r["pos"] = a["pos"][:npnt]; r["uv"] = a["uv"][:npnt] if m.has_uv else None; r["nrm"] = a["nrm"][:npnt] if m.has_nrm else None
+            res.append(r)
         return res
 
     # ---- measurement ----
