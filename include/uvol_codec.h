@@ -385,8 +385,9 @@ int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const s
  * against the corners of its position entry).  Sequential files (`-cl 0`) go through the same entry and come out under the same numbering.
  * Output memory as in the existing decode: device pointers when outputs_on_device (written in place by the weld kernels, no copy);
  * pageable host arrays through the pinned double buffers; arrays that ALL lie in uvol_host_alloc memory written by DMA where they are.
- * Out of scope: material ids on this form (use uvol_decode_mesh_batch_mat: its face order is the same); quantised or half-float vertex
- * formats.  uvol_decode_mesh_batch, _dev and _mat are unchanged: they launch none of the weld kernels and carve none of their scratch. */
+ * Out of scope on this float form: material ids (uvol_decode_mesh_batch_packed below carries them; uvol_decode_mesh_batch_mat returns them
+ * per face, in the same face order); half-float vertex formats.  uvol_decode_mesh_batch, _dev and _mat are unchanged: they launch none
+ * of the weld kernels and carve none of their scratch. */
 enum { UVOL_POINTS_PLANAR = 0, UVOL_POINTS_INTERLEAVED = 1 };
 typedef struct uvol_decoded_points {
   /* in */
@@ -401,6 +402,48 @@ typedef struct uvol_decoded_points {
 } uvol_decoded_points;
 int uvol_decode_mesh_batch_points(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                   uvol_decoded_points *out, int *status);
+
+/* ---- packed render-ready form: 16-byte records of the file's own integers, with material ids (additive: uvol_abi_version stays 1) ----
+ * A .drc file stores positions and tex-coords as small integers (11 and 10 bits in every recorded file); the float form above turns them
+ * into 32-bit floats and has no slot for the material id.  This entry point hands a renderer that feeds normalised-integer vertex formats
+ * (KHR_mesh_quantization style) the integers themselves, exactly, in half the bytes.  Points, their numbering and `index` are those of
+ * uvol_decode_mesh_batch_points on the same file.  Record of point p, 16 bytes, little endian:
+ *   bytes  0 -  5   uint16 px, py, pz   the file's quantised position integers of p's position entry, unchanged
+ *   bytes  6 -  7   uint16 material     the material id of p (0 when has_material is 0)
+ *   bytes  8 - 11   uint16 u, v         the file's quantised tex-coord integers (zeros when the file has no tex-coords)
+ *   bytes 12 - 15   int8 nx, ny, nz, 0  rintf(n[k] * 127.0f), round to nearest even, n = the float normal uvol_decode_mesh_batch_points returns
+ *                                       for that entry, bit for bit (zeros when the file has no normals)
+ * Dequantisation, all in IEEE binary32 with the product rounded BEFORE the sum (two roundings, no fused multiply-add):
+ *   position k = pos_min[k] + (float)q[k] * pos_scale,   pos_scale = range / (float)((1u << pos_bits) - 1)
+ *   tex-coord k = uv_min[k] + (float)q[k] * uv_scale,    uv_scale  = range / (float)((1u << uv_bits) - 1)
+ * which reproduces the floats of uvol_decode_mesh_batch[_points] bit for bit (the checker's drc_dequant evaluates the same expression, built
+ * with floating-point contraction off; tests/test_hipemu_packed.py asserts it against NumPy).  A shader that fuses the two differs by at
+ * most one unit in the last place.  pos_min / uv_min are the attribute's minimum values as the file stores them.
+ * Material: the attribute uvol_decode_mesh_batch_mat reads (GENERIC uint8, one component, a vertex attribute on the base corner table of
+ * an edgebreaker file), under the same condition for has_material.  Its entry is a function of the position entry, so it never splits a
+ * point; `material` is its value at the point's first corner.  A generic attribute of any other shape: has_material = 0, slot zero.
+ * records == NULL or index == NULL skips that output.  A DEVICE records buffer must be 16-byte aligned (one 16-byte store per point); a
+ * misaligned one in any frame fails the whole call with UVOL_E_INVALID before anything runs.  Capacity and per-frame statuses as in the
+ * float form: UVOL_E_NOSPACE (points or faces exceed the capacities: n_points / n_faces are the needed counts, nothing of the frame is
+ * written), UVOL_E_INVALID (foreign file), UVOL_E_ENCODE (corrupt file), UVOL_E_UNSUPPORTED (a position entry shared by more than 4096
+ * corners) and, of this form alone, UVOL_E_UNSUPPORTED for a position or tex-coord attribute that is not quantised or is quantised to more
+ * than 16 bits (uvol_last_error names the attribute; nothing of the frame is written).  Sequential (`-cl 0`) files go through the same
+ * entry.  Output memory: the three forms of the float entry point.  The float value arrays are neither carved nor written on this path. */
+typedef struct uvol_packed_points {
+  /* in */
+  uint32_t cap_faces;              /* index holds 3 * cap_faces entries */
+  size_t cap_points;               /* records holds 16 * cap_points bytes */
+  void *records;                   /* 16 bytes per point, layout above; NULL skips it */
+  uint32_t *index;                 /* one point id per corner; NULL skips it */
+  /* out */
+  uint32_t n_faces, n_points;
+  uint32_t has_uv, has_nrm, has_material;
+  uint32_t pos_bits, uv_bits;      /* quantisation bits of the file; uv_bits 0 when absent */
+  float pos_min[3], pos_scale;     /* position k = pos_min[k] + q[k] * pos_scale */
+  float uv_min[2], uv_scale;
+} uvol_packed_points;
+int uvol_decode_mesh_batch_packed(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
+                                  uvol_packed_points *out, int *status);
 
 /* ---- measurement hooks (bench.py / rocprof cross-check) ---- */
 /* When enabled, every kernel group is bracketed by hipEvents on the ctx stream. */

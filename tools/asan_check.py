@@ -48,6 +48,12 @@ import points_cases as PC
 c0p = uvol.Codec(lib_path=lib, DRACO_COMPRESSION_LEVEL=0)
 PC.run_subsets(o, cd, c0p); PC.run_ragged(o, cd, c0p); PC.run_long_fan(o, cd, c0p); PC.run_memory_forms(o, cd, c0p, MC.HostMem(), lib_path=lib)
 PC.run_recorded(o, cd, [open(os.path.join(ROOT, "tests", "golden", n), "rb").read() for n in ("00000.drc", "00075.drc")])
+# packed records (tests/test_hipemu_packed.py's checks): k_weld_packed_check / k_weld_write_packed, the integers and the two maps kept alive
+# up to the weld, the 16-byte staging, refused frames among device outputs, material streams, one recorded file
+import packed_cases as KC
+KC.run_subsets(o, cd, c0p); KC.run_materials(o, cd); KC.run_ragged(o, cd, c0p, MC.HostMem()); KC.run_wide_quantisation(o, cd)
+KC.run_memory_forms(o, cd, c0p, MC.HostMem(), lib_path=lib)
+KC.run_recorded(o, cd, KC.golden("00000.drc"))
 c0p.close()
 # corrupted decoder inputs: bit flips, truncations, overwritten words - a clean error or a decoded result, never an out-of-bounds access
 rng = np.random.default_rng(5)

@@ -5,8 +5,13 @@ the three alternated in fresh child processes; every child times REPEATS calls a
 `rocprofv3 --kernel-trace --stats` and, each in a pass of its own, under `--pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (fewer frames: the
 counters serialise the kernels).  Writes profiles/r08_points_decode.json.
 
+--packed: uvol_decode_mesh_batch_packed (16-byte integer records) against the float interleaved form of this build and of the parent build,
+to three destinations - HBM, pageable host arrays, arrays in uvol_host_alloc memory -, alternated in fresh child processes in the same
+session; the output arrays are allocated and touched once per process, outside the timed calls.  Writes profiles/r07_packed_points.json.
+
 usage: tools/points_timing.py [n_frames] --parent-lib PATH [--pairs 3] [--prof-frames 240] [--out FILE]   (driver: starts the children, never opens the GPU)
-       tools/points_timing.py [n_frames] --child points|dev [--lib PATH]                                  (one measurement, one JSON line)"""
+       tools/points_timing.py [n_frames] --packed --parent-lib PATH [--pairs 3] [--out FILE]               (driver of the packed comparison)
+       tools/points_timing.py [n_frames] --child points|dev|packed [--dest dev|host|pinned] [--lib PATH]  (one measurement, one JSON line)"""
 import argparse, collections, csv, ctypes as C, glob, json, os, re, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "universal-volumetric_amd"))
@@ -78,6 +83,63 @@ def child(n, mode, lib):
     print("RESULT " + json.dumps(res))
 
 
+def child_packed(n, dest, lib):
+    """Float interleaved records and, where the library has it, packed records of n frames into `dest` memory."""
+    import numpy as np, synth, uvol
+    c = uvol.Codec(device=0, max_batch=n, lib_path=lib)
+    distinct = c.encode_mesh_batch([synth.sphere_mesh(frame=k) for k in range(4)])
+    files = [distinct[i % 4] for i in range(n)]
+    nfs = [c.drc_info(f)[0] for f in distinct]; pts = [r["n_points"] for r in c.decode_mesh_batch_points(distinct)]
+    has_packed = hasattr(c.L, "uvol_decode_mesh_batch_packed")
+    fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
+    total = sum(512 + 32 * pts[i % 4] + 12 * nfs[i % 4] for i in range(n)) + 4096
+    if dest == "dev": mem = Hbm(total); take = mem.take
+    elif dest == "pinned": mem = uvol.PinnedArena(total, lib_path=lib); take = lambda nb: mem.take((nb,), np.uint8).ctypes.data
+    else:
+        keep = []
+        def take(nb):
+            a = np.zeros(nb, np.uint8); keep.append(a); return a.ctypes.data      # (zeros: every page is touched before the first timed call)
+    res = dict(mode="packed", dest=dest, frames=n, lib=os.path.basename(os.path.dirname(lib)) if lib else "this build", points_per_frame=pts, faces_per_frame=nfs)
+    bufs = [(take(32 * pts[i % 4]), take(12 * nfs[i % 4])) for i in range(n)]      # the packed form writes the first half of the same record buffers
+    fm = (uvol.DecodedPoints * n)(); pm = (uvol.PackedPoints * n)()
+    for i in range(n):
+        fm[i].cap_faces = pm[i].cap_faces = nfs[i % 4]; fm[i].cap_points = pm[i].cap_points = pts[i % 4]; fm[i].layout = uvol.UVOL_POINTS_INTERLEAVED
+        fm[i].pos = pm[i].records = bufs[i][0]; fm[i].index = pm[i].index = bufs[i][1]
+    on_dev = 1 if dest == "dev" else 0
+    runs = [("interleaved", lambda: c.L.uvol_decode_mesh_batch_points(c.h, fp, ln, n, on_dev, fm, st), sum(32 * pts[i % 4] + 12 * nfs[i % 4] for i in range(n)))]
+    if has_packed: runs.append(("packed", lambda: c.L.uvol_decode_mesh_batch_packed(c.h, fp, ln, n, on_dev, pm, st), sum(16 * pts[i % 4] + 12 * nfs[i % 4] for i in range(n))))
+    for name, run, nbytes in runs:
+        assert run() == 0 and list(st) == [0] * n, (name, list(st)[:8])       # warm-up: allocates the workspaces of the whole batch
+        ms = []
+        for _ in range(REPEATS):
+            t = time.perf_counter(); rc = run(); ms.append(1000 * (time.perf_counter() - t)); assert rc == 0
+        c.profile(True); c.profile_reset(); run()
+        groups = {g["name"]: round(g["total_ms"], 2) for g in c.profile_report() if g["launches"]}
+        c.profile(False)
+        res[name] = dict(frames_per_s=n / (min(ms) / 1000), frames_per_s_calls=[round(n / (x / 1000), 1) for x in ms], ms_calls=[round(x, 2) for x in ms], output_bytes_per_call=nbytes, groups_ms=groups)
+    if dest == "dev": mem.free()
+    elif dest == "pinned": mem.close()
+    c.close()
+    print("RESULT " + json.dumps(res))
+
+
+def main_packed(a):
+    out = dict(frames_per_call=a.n, repeats_per_process=REPEATS, rounds=[], note="alternated in fresh processes, per destination: this build (float interleaved records, "
+               "then packed records) / the parent build (float interleaved records); frames_per_s is the best of the process's calls, frames_per_s_calls all of them")
+    for k in range(a.pairs):
+        rnd = {}
+        for dest in ("dev", "host", "pinned"):
+            for who, lib in (("this", None), ("parent", a.parent_lib)):
+                cmd = [sys.executable, os.path.abspath(__file__), str(a.n), "--child", "packed", "--dest", dest] + (["--lib", lib] if lib else [])
+                r = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
+                if r.returncode != 0:
+                    raise SystemExit("child %s/%s failed (%d): %s" % (dest, who, r.returncode, r.stderr[-2000:]))      # nothing more is started after a failure
+                rnd[dest + "_" + who] = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+        out["rounds"].append(rnd)
+        print(json.dumps({k2: {nm: round(v["frames_per_s"], 1) for nm, v in p.items() if isinstance(v, dict) and "frames_per_s" in v} for k2, p in rnd.items()}), flush=True)
+        json.dump(out, open(a.out, "w"), indent=1)
+
+
 def weld_rows(d, suffix, value):
     """{kernel: value(row)} of the k_weld_* rows of the rocprofv3 CSV `*suffix` under d."""
     f = glob.glob(os.path.join(d, "**", "*" + suffix), recursive=True)
@@ -92,10 +154,15 @@ def weld_rows(d, suffix, value):
 def main():
     ap = argparse.ArgumentParser(); ap.add_argument("n", nargs="?", type=int, default=1920); ap.add_argument("--child"); ap.add_argument("--lib")
     ap.add_argument("--parent-lib"); ap.add_argument("--pairs", type=int, default=3); ap.add_argument("--prof-frames", type=int, default=240)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r08_points_decode.json"))
+    ap.add_argument("--out"); ap.add_argument("--packed", action="store_true"); ap.add_argument("--dest", default="dev", choices=("dev", "host", "pinned"))
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "r07_packed_points.json" if a.packed else "r08_points_decode.json")
+    if a.child == "packed":
+        return child_packed(a.n, a.dest, a.lib)
     if a.child:
         return child(a.n, a.child, a.lib)
+    if a.packed:
+        return main_packed(a)
     out = dict(frames_per_call=a.n, repeats_per_process=REPEATS, pairs=[], note="alternated in fresh processes: this build's uvol_decode_mesh_batch_points "
                "(device outputs) / the parent build's and this build's uvol_decode_mesh_batch_dev; frames_per_s is the best of ms_calls; groups_ms are the "
                "library's event brackets of one further call")

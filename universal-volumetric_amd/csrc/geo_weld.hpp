@@ -16,6 +16,8 @@
 //   k_weld_rep      representative = lowest corner of the fan with equal (uv, normal) entries; first-appearance flags scanned per block
 //   k_weld_sums     again for the flags -> point ids, n_points
 //   k_weld_write    index[c] = point of the representative; the first corner of a point gathers its values (bit copies, no arithmetic)
+// uvol_decode_mesh_batch_packed runs the same stages up to the point ids, k_weld_packed_check ahead of them and k_weld_write_packed in
+// place of k_weld_write: 16-byte records of the integers the file holds (no dequantised float is read: none is written on that path).
 // A position entry shared by more than GW_MAXFAN corners fails its frame (GW_E_FAN -> UVOL_E_UNSUPPORTED): the pairwise compare is
 // quadratic in the fan, and a longer one would turn one thread into a serial chain.  This is a limit of this entry point alone: such a
 // file (a sequential, `-cl 0`, stream can hold one) still decodes through uvol_decode_mesh_batch.  The largest fan of the recorded files
@@ -25,6 +27,9 @@
 #define GW_MAXFAN 4096
 #define GW_E_FAN (-41)
 #define GW_E_NOPOS (-42)
+#define GW_E_PK_POS (-43)      // packed records: the position attribute is not quantised to 1 .. 16 bits (or has not 3 components)
+#define GW_E_PK_UV (-44)       //                 the same of the tex-coord attribute (2 components)
+#define GW_E_PK_NRM (-45)      //                 a normal attribute that is neither octahedral nor of 3 components
 
 struct GWView { const uint32_t *ip, *iu, *in; uint32_t nc, np, has_uv, has_nrm; };
 // np = 0 (every kernel idles) unless the frame decoded, carries positions and its entries fit the counters
@@ -142,4 +147,53 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_weld_write(GeoDecJob *jobs) {
   if (J.w.o_val[0]) { uint32_t *o = reinterpret_cast<uint32_t *>(J.w.o_val[0]) + 3 * (size_t)id; o[0] = pv[0]; o[1] = pv[1]; o[2] = pv[2]; }
   if (J.w.o_val[1] && uv) { uint32_t *o = reinterpret_cast<uint32_t *>(J.w.o_val[1]) + 2 * (size_t)id; o[0] = uv[0]; o[1] = uv[1]; }
   if (J.w.o_val[2] && nv) { uint32_t *o = reinterpret_cast<uint32_t *>(J.w.o_val[2]) + 3 * (size_t)id; o[0] = nv[0]; o[1] = nv[1]; o[2] = nv[2]; }
+}
+
+// ---- packed records (uvol_decode_mesh_batch_packed) ----
+// One thread per frame, ahead of the weld: can the frame's integers go into uint16 slots?  A frame that fails here is skipped by every
+// weld kernel (status != 0) and none of its outputs is written.  Also picks the material decoder (k_gdec_facemat's rule).
+__global__ void __launch_bounds__(64) k_weld_packed_check(GeoDecJob *jobs) {
+  GeoDecJob &J = jobs[blockIdx.x];
+  if (threadIdx.x != 0 || !J.w.on || J.status != 0) return;
+  J.w.mat_dec = gd_mat_decoder(J);
+  if (J.o_dec[0] < 0) return;                               // (no position attribute: k_weld_clear reports it)
+  { const GDAtt &A = J.att[J.o_dec[0]]; if (A.seq_type != 2 || A.ncomp != 3 || A.qbits < 1 || A.qbits > 16) { J.status = GW_E_PK_POS; return; } }
+  if (J.o_dec[1] >= 0) { const GDAtt &A = J.att[J.o_dec[1]]; if (A.seq_type != 2 || A.ncomp != 2 || A.qbits < 1 || A.qbits > 16) { J.status = GW_E_PK_UV; return; } }
+  if (J.o_dec[2] >= 0) { const GDAtt &A = J.att[J.o_dec[2]]; if (A.seq_type != 3 && A.ncomp != 3) { J.status = GW_E_PK_NRM; return; } }
+}
+
+// rintf(v * 127) as the low byte of an int8 (round to nearest even, the default mode); a value past the int8 range - no unit normal has one - saturates
+__device__ __forceinline__ uint32_t gw_snorm8(float v) {
+  const float r = rintf(v * 127.0f);
+  return (uint32_t)(int32_t)fminf(fmaxf(r, -128.0f), 127.0f) & 0xffu;
+}
+
+// index[c] = point of the representative; the first corner of a point gathers the point's record:
+//   uint16 px py pz | uint16 material | uint16 u v | int8 nx ny nz 0      - one aligned 16-byte store per point, absent slots zero
+// The integers come straight from the decoders' vals arrays (kept alive up to this stage on the packed path, gdec_carve); the normal is
+// the float of gd_oct_normal / k_gdec_finish's expressions, rounded here.
+__global__ void __launch_bounds__(UVOL_BLOCK) k_weld_write_packed(GeoDecJob *jobs, const GeoJob *gj) {
+  GeoDecJob &J = jobs[blockIdx.y]; const GeoJob &G = gj[blockIdx.y];
+  const GWView V = gw_view(J);
+  const uint32_t c = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (J.status != 0 || V.np == 0 || c >= V.nc || J.w.np > J.w.cap) return;      // a frame whose points do not fit is left alone (UVOL_E_NOSPACE)
+  const uint32_t r = J.w.rep[c], id = J.w.bsum_c[r / UVOL_BLOCK] + J.w.pid[r];
+  if (J.w.o_index) J.w.o_index[c] = id;
+  if (r != c || !J.w.o_val[0]) return;
+  const int32_t *pv = J.att[J.o_dec[0]].vals + 3 * (size_t)V.ip[c];
+  const uint32_t mat = J.w.mat_dec >= 0 ? (uint32_t)gd_mat_value(J, G, J.w.mat_dec, c) : 0u;
+  uint4 rec;
+  rec.x = ((uint32_t)pv[0] & 0xffffu) | ((uint32_t)pv[1] << 16);
+  rec.y = ((uint32_t)pv[2] & 0xffffu) | (mat << 16);
+  rec.z = 0; rec.w = 0;
+  if (V.has_uv) { const int32_t *uv = J.att[J.o_dec[1]].vals + 2 * (size_t)V.iu[c]; rec.z = ((uint32_t)uv[0] & 0xffffu) | ((uint32_t)uv[1] << 16); }
+  if (V.has_nrm) {
+    const GDAtt &A = J.att[J.o_dec[2]]; const size_t i = V.in[c];
+    float n[3];
+    if (A.seq_type == 3) gd_oct_normal(A, i, n[0], n[1], n[2]);
+    else if (A.seq_type == 2) { const float delta = gd_delta(A); for (int k = 0; k < 3; k++) n[k] = A.minv[k] + (float)A.vals[3 * i + k] * delta; }
+    else for (int k = 0; k < 3; k++) n[k] = (float)A.vals[3 * i + k];
+    rec.w = gw_snorm8(n[0]) | (gw_snorm8(n[1]) << 8) | (gw_snorm8(n[2]) << 16);
+  }
+  reinterpret_cast<uint4 *>(J.w.o_val[0])[id] = rec;        // id < np <= cap <= the caller's cap_points
 }

@@ -14,7 +14,7 @@
 //   k_gdec_rans     again for the attribute symbol streams (their lengths are the traversal results)
 //   k_gdec_pred     1 lane / (decoder, frame)   parallelogram / tex-coord-portable / geometric-normal prediction + transforms
 //   k_gdec_finish   parallel           dequantisation (fp32, octahedral) and per-corner entry indices
-//   k_weld_*        parallel           uvol_decode_mesh_batch_points only (geo_weld.hpp): one index per corner + one value record per point
+//   k_weld_*        parallel           uvol_decode_mesh_batch_points / _packed only (geo_weld.hpp): one index per corner + one value record per point
 #include "uvol_common.hpp"
 #include "geom_device.hpp"
 #include "uvol_ws.hpp"
@@ -36,9 +36,10 @@ struct GDAtt {
   int32_t *vals;                 // ne * nc decoded integers, entry order
   GDRabs aux;                    // uv orientation bits / normal flip bits
 };
-// weld stage (geo_weld.hpp; uvol_decode_mesh_batch_points): scratch, outputs and results of one frame; all zero for the other entry points
+// weld stage (geo_weld.hpp; uvol_decode_mesh_batch_points / _packed): scratch, outputs and results of one frame; all zero for the other entry points
 struct GDWeldJob {
   uint32_t on, layout, cap, np;        // layout: UVOL_POINTS_*; cap: points the value outputs hold; np: points of the frame (out)
+  uint32_t packed; int32_t mat_dec;    // packed: 16-byte records of the file's integers (o_val[0] is the one buffer); mat_dec: decoder of the material attribute or -1 (out)
   uint32_t *cnt, *fan, *rep, *pid, *bsum_p, *bsum_c;
   float *o_val[3]; uint32_t *o_index;  // planar: pos / uv / nrm (any may be null); interleaved: o_val[0] is the one buffer
 };
@@ -969,7 +970,22 @@ __global__ void __launch_bounds__(64) k_gdec_counts(GeoDecJob *jobs, GeoJob *gj)
   }
 }
 
+// Unit normal of octahedral entry i (seq_type 3).  k_gdec_finish and k_weld_write_packed (geo_weld.hpp) both call this and nothing else,
+// so the float a packed record rounds is the float the other entry points return, bit for bit.
+__device__ __forceinline__ void gd_oct_normal(const GDAtt &A, size_t i, float &x, float &y, float &z) {
+  const GOct ot = g_oct(A.qbits);
+  y = (float)A.vals[2 * i] * (2.0f / (float)ot.MAXV) - 1.0f; z = (float)A.vals[2 * i + 1] * (2.0f / (float)ot.MAXV) - 1.0f;
+  x = 1.0f - fabsf(y) - fabsf(z); const float xo = x < 0 ? -x : 0;
+  y += y < 0 ? xo : -xo; z += z < 0 ? xo : -xo;
+  const float nn = sqrtf(x * x + y * y + z * z);
+  if (nn > 1e-6f) { x /= nn; y /= nn; z /= nn; } else { x = y = z = 0; }
+}
+// step of a quantised attribute (seq_type 2): value k of an entry = minv[k] + (float)q[k] * delta, the product rounded before the sum
+__device__ __host__ __forceinline__ float gd_delta(const GDAtt &A) { return A.range / (float)((1u << A.qbits) - 1); }
+
 // ---- K10: outputs.  blockIdx.z = 0 position, 1 tex-coord, 2 normal ----
+// The per-corner entry indices always; the float values only where the frame has an array for them (o_val[which]: null on the packed path,
+// whose records take the integers of A.vals - no float array is carved or written there).
 __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_finish(GeoDecJob *jobs, GeoJob *gj) {
   GeoDecJob &J = jobs[blockIdx.y]; const GeoJob &G = gj[blockIdx.y];
   if (J.status != 0) return;
@@ -985,15 +1001,10 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_finish(GeoDecJob *jobs, Geo
   if (i >= ne || !J.o_val[which]) return;
   float *o = J.o_val[which];
   if (A.seq_type == 2) {
-    const float delta = A.range / (float)((1u << A.qbits) - 1);
+    const float delta = gd_delta(A);
     for (int k = 0; k < A.ncomp; k++) o[(size_t)i * A.ncomp + k] = A.minv[k] + (float)A.vals[(size_t)i * A.ncomp + k] * delta;
   } else if (A.seq_type == 3) {
-    const GOct ot = g_oct(A.qbits);
-    float y = (float)A.vals[2 * (size_t)i] * (2.0f / (float)ot.MAXV) - 1.0f, z = (float)A.vals[2 * (size_t)i + 1] * (2.0f / (float)ot.MAXV) - 1.0f;
-    float x = 1.0f - fabsf(y) - fabsf(z); const float xo = x < 0 ? -x : 0;
-    y += y < 0 ? xo : -xo; z += z < 0 ? xo : -xo;
-    const float nn = sqrtf(x * x + y * y + z * z);
-    if (nn > 1e-6f) { x /= nn; y /= nn; z /= nn; } else { x = y = z = 0; }
+    float x, y, z; gd_oct_normal(A, i, x, y, z);
     o[3 * (size_t)i] = x; o[3 * (size_t)i + 1] = y; o[3 * (size_t)i + 2] = z;
   } else for (int k = 0; k < A.ncomp; k++) o[(size_t)i * A.ncomp + k] = (float)A.vals[(size_t)i * A.ncomp + k];
 }
@@ -1001,16 +1012,22 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_finish(GeoDecJob *jobs, Geo
 // Material ids (thread per face): the value of the entry of the face's first corner, for the first decoder that holds a GENERIC (4) UINT8 (2)
 // one-component attribute on the base table (a vertex attribute, dec_type 0) of an edgebreaker file - what stock draco_encoder writes for
 // `usemtl` lines while no two materials meet at a vertex.  A generic attribute of another shape decodes as before and reports no material.
+// gd_mat_decoder / gd_mat_value are the one statement of that rule: k_gdec_facemat and the packed weld (geo_weld.hpp) both go through them.
+__device__ __forceinline__ int gd_mat_decoder(const GeoDecJob &J) {
+  if (J.method != 1) return -1;
+  for (int k = 0; k < J.ndec; k++) { const GDAtt &A = J.att[k]; if (A.att_type == 4 && A.data_type == 2 && A.ncomp == 1 && A.dec_type == 0 && A.table == 0 && A.seq_type == 1) return k; }
+  return -1;
+}
+__device__ __forceinline__ uint8_t gd_mat_value(const GeoDecJob &J, const GeoJob &G, int d, size_t corner) { return (uint8_t)J.att[d].vals[G.v2d[0][J.c2v[corner]]]; }
 __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_facemat(GeoDecJob *jobs, GeoJob *gj) {
   GeoDecJob &J = jobs[blockIdx.y]; const GeoJob &G = gj[blockIdx.y];
-  if (J.status != 0 || J.method != 1) return;
-  int d = -1;
-  for (int k = 0; k < J.ndec; k++) { const GDAtt &A = J.att[k]; if (A.att_type == 4 && A.data_type == 2 && A.ncomp == 1 && A.dec_type == 0 && A.table == 0 && A.seq_type == 1) { d = k; break; } }
+  if (J.status != 0) return;
+  const int d = gd_mat_decoder(J);
   if (d < 0) return;
   const uint32_t f = blockIdx.x * UVOL_BLOCK + threadIdx.x;
   if (f == 0) J.o_has_mat = 1;
   if (f >= (uint32_t)J.nf) return;
-  J.o_mat[f] = (uint8_t)J.att[d].vals[G.v2d[0][J.c2v[3 * (size_t)f]]];
+  J.o_mat[f] = gd_mat_value(J, G, d, 3 * (size_t)f);
 }
 
 #define GEO_SCAN_BLOCK_ONLY
@@ -1076,17 +1093,20 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_clear(GeoDecJob *jobs) {
 // with the worst case (3 x faces).  265 -> ~90 MB per 200 k-face frame.
 // weld: 0 none (every entry point but uvol_decode_mesh_batch_points: nothing of the weld is carved), 1 scratch, 2 scratch + staging of the
 // outputs (host outputs).  The weld runs when everything else is dead - its inputs, the arrays k_gdec_finish wrote, lie in the output area -,
-// so its arrays share the addresses of the predictors' and the frame's peak does not grow.
+// so its arrays share the addresses of the predictors' and the frame's peak does not grow.  3 / 4: the same two for
+// uvol_decode_mesh_batch_packed - 16 bytes of staging per point, and the decoded integers (att[].vals) and the two maps the material fetch
+// reads (c2v, v2d[0]) stay alive up to the weld, which gathers them; the other entry points' placement does not change.
 enum { DS_INDEX = 0, DS_CTX, DS_CONN, DS_TABLES, DS_TRAV, DS_SYM, DS_PRED, DS_FIN, DS_WELD, DS_COUNT };
 struct GDWeldStage { uint32_t *index; uint8_t *vals; };
 static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool full, GDPlan &P, int weld = 0, GDWeldStage *stage = nullptr) {
   const size_t nf = (size_t)J.nf, nc = 3 * nf, maxv = (size_t)J.nev + nf + 8;          // nsplit <= nf
   const size_t E = full ? nc + 3 : std::min(nc + 3, nf + nf / 2 + 4096);
+  const bool packed = weld >= 3; const int DS_VALS = packed ? DS_WELD : DS_FIN;
   J.ecap = (uint32_t)E;
   std::vector<UvolWsItem> items; std::vector<void **> slots;
 #define DCARVE(field, bytes, first, last) do { items.push_back(UvolWsItem{ (size_t)(bytes), (first), (last), 0 }); slots.push_back((void **)&(field)); } while (0)
   DCARVE(J.sp_src, 4 * (nf + 1), DS_INDEX, DS_CONN); DCARVE(J.sp_spl, 4 * (nf + 1), DS_INDEX, DS_CONN); DCARVE(J.sp_edge, nf + 8, DS_INDEX, DS_CONN);
-  DCARVE(J.opp, 4 * nc, DS_INDEX, DS_FIN); DCARVE(J.c2v, 4 * nc, DS_INDEX, DS_FIN);
+  DCARVE(J.opp, 4 * nc, DS_INDEX, DS_FIN); DCARVE(J.c2v, 4 * nc, DS_INDEX, DS_VALS);
   DCARVE(J.lm, 4 * maxv, DS_CONN, DS_TABLES); DCARVE(J.val, 4 * maxv, UVOL_WS_PINNED, UVOL_WS_PINNED);
   DCARVE(J.stack, 4 * (nf + 8), DS_CONN, DS_CONN); DCARVE(J.tsac, 4 * (nf + 2), DS_INDEX, DS_CONN);
   for (int k = 0; k < GD_MAXAD; k++) { DCARVE(J.edge_seam[k], nc, UVOL_WS_PINNED, UVOL_WS_PINNED); DCARVE(J.t_c2v[k], 4 * nc, DS_INDEX, DS_FIN); DCARVE(J.t_lm[k], 4 * E, DS_TABLES, DS_TABLES); }
@@ -1099,15 +1119,15 @@ static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool f
     // (written from the traversal stage on: the early pass of the symbol decoder runs beside the traversals)
     DCARVE(S.probs, 4 * (size_t)GD_MAX_NS, DS_CTX, DS_SYM); DCARVE(S.cum, 4 * (size_t)GD_MAX_NS, DS_CTX, DS_SYM); DCARVE(S.lut, 4 * (size_t)(1u << 20), DS_CTX, DS_SYM);
     // (the last slot also holds the index differences of a frame with compressed sequential connectivity: one per corner)
-    DCARVE(S.out, 4 * (std::max(4 * E, k == GD_MAXDEC - 1 ? nc : (size_t)0) + 4), DS_CTX, DS_PRED); DCARVE(J.att[k].vals, 4 * (4 * E + 4), DS_PRED, DS_FIN);
+    DCARVE(S.out, 4 * (std::max(4 * E, k == GD_MAXDEC - 1 ? nc : (size_t)0) + 4), DS_CTX, DS_PRED); DCARVE(J.att[k].vals, 4 * (4 * E + 4), DS_PRED, DS_VALS);
   }
   for (int k = 1; k < 4; k++) DCARVE(G.rec[k], (r8 ? 32 : 64) * (nf + 1), DS_TRAV, DS_TRAV);     // 8- or 16-byte corner records, decided per batch (geo_records8)
-  for (int k = 0; k < 3; k++) { DCARVE(G.order[k], 4 * (E + 3), DS_TRAV, DS_FIN); DCARVE(G.v2d[k], 4 * (std::max(E, maxv) + 3), DS_TRAV, DS_FIN); DCARVE(G.t_stack[k], 4 * (nf + 2), DS_TRAV, DS_TRAV); DCARVE(G.t_vvis[k], std::max(E, maxv) / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); DCARVE(G.t_fvis[k], nf / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); }
+  for (int k = 0; k < 3; k++) { DCARVE(G.order[k], 4 * (E + 3), DS_TRAV, DS_FIN); DCARVE(G.v2d[k], 4 * (std::max(E, maxv) + 3), DS_TRAV, k == 0 ? DS_VALS : DS_FIN); DCARVE(G.t_stack[k], 4 * (nf + 2), DS_TRAV, DS_TRAV); DCARVE(G.t_vvis[k], std::max(E, maxv) / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); DCARVE(G.t_fvis[k], nf / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); }
   GDWeldStage stg{ nullptr, nullptr };
   if (weld) {
     DCARVE(J.w.cnt, 4 * (E + 2), DS_WELD, DS_WELD); DCARVE(J.w.fan, 4 * nc, DS_WELD, DS_WELD); DCARVE(J.w.rep, 4 * nc, DS_WELD, DS_WELD); DCARVE(J.w.pid, 4 * nc, DS_WELD, DS_WELD);
     DCARVE(J.w.bsum_p, 4 * (E / UVOL_BLOCK + 4), DS_WELD, DS_WELD); DCARVE(J.w.bsum_c, 4 * (nc / UVOL_BLOCK + 4), DS_WELD, DS_WELD);
-    if (weld == 2) { DCARVE(stg.index, 4 * nc, DS_WELD, DS_WELD); DCARVE(stg.vals, 32 * nc, DS_WELD, DS_WELD); }      // (n_points <= corners)
+    if (weld == 2 || weld == 4) { DCARVE(stg.index, 4 * nc, DS_WELD, DS_WELD); DCARVE(stg.vals, (packed ? 16 : 32) * nc, DS_WELD, DS_WELD); }      // (n_points <= corners)
   }
 #undef DCARVE
   const std::vector<uint64_t> key = { (uint64_t)nf, (uint64_t)J.nev, (uint64_t)r8 | ((uint64_t)full << 1) | ((uint64_t)weld << 2), (uint64_t)items.size() };
@@ -1122,8 +1142,9 @@ static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool f
 }
 
 // pts: uvol_decode_mesh_batch_points (the weld stage runs and fills pts[i]; `out` then only carries capacities, its arrays are null)
+// pk: uvol_decode_mesh_batch_packed (the same with 16-byte integer records; k_gdec_finish writes the index streams alone)
 static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev,
-                                 uint8_t *const *fmat = nullptr, int *has_mat = nullptr, uvol_decoded_points *pts = nullptr);
+                                 uint8_t *const *fmat = nullptr, int *has_mat = nullptr, uvol_decoded_points *pts = nullptr, uvol_packed_points *pk = nullptr);
 int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool outputs_on_device,
                      uint8_t *const *face_material, int *has_material) {
   return geo_decode_batch_impl(ctx, files, lens, n, out, status, false, outputs_on_device, face_material, has_material);
@@ -1139,10 +1160,20 @@ int geo_decode_points(uvol_ctx *ctx, const uint8_t *const *files, const size_t *
   }
   return geo_decode_batch_impl(ctx, files, lens, n, meshes.data(), status, false, outputs_on_device, nullptr, nullptr, pts);
 }
+// the same for packed records; further UVOL_E_UNSUPPORTED for a position / tex-coord attribute that does not fit uint16 slots
+int geo_decode_packed(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_packed_points *pk, int *status, bool outputs_on_device) {
+  std::vector<uvol_decoded_mesh> meshes((size_t)(n > 0 ? n : 0), uvol_decoded_mesh{});
+  for (int i = 0; i < n; i++) {
+    uint32_t nev = 0, nf = 0;
+    if (!gdec_header(files[i], lens[i], &nev, &nf)) { ctx->set_error("frame %d: not a Draco 2.2 mesh", i); return UVOL_E_INVALID; }
+    meshes[(size_t)i].cap_faces = nf; meshes[(size_t)i].cap_values = 3 * (size_t)nf;
+  }
+  return geo_decode_batch_impl(ctx, files, lens, n, meshes.data(), status, false, outputs_on_device, nullptr, nullptr, nullptr, pk);
+}
 static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_mesh *out, int *status, bool full, bool out_dev,
-                                 uint8_t *const *fmat, int *has_mat, uvol_decoded_points *pts) {
+                                 uint8_t *const *fmat, int *has_mat, uvol_decoded_points *pts, uvol_packed_points *pk) {
   const bool want_mat = fmat != nullptr || has_mat != nullptr;
-  const int weld = pts ? (out_dev ? 1 : 2) : 0;
+  const int weld = pts ? (out_dev ? 1 : 2) : pk ? (out_dev ? 3 : 4) : 0;
   GeoDecState *T = ctx->geodec;
   if (n <= 0) return UVOL_OK;
   T->hjobs.assign((size_t)n, GeoDecJob{}); T->hg.assign((size_t)n, GeoJob{});
@@ -1160,7 +1191,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     foff[i] = ftot; ftot += a256(lens[i] + 16);
     GeoJob gtmp{}; const size_t w = gdec_carve(J, gtmp, nullptr, r8, full, T->plan, weld);
     woff[i] = wtot; wtot += a256(w);
-    { const size_t nc = 3 * (size_t)nf; ooff[i] = otot; otot += 3 * (a256(4 * 3 * nc) + a256(4 * nc)) + (want_mat ? a256(nf) : 0); }
+    { const size_t nc = 3 * (size_t)nf; ooff[i] = otot; otot += 3 * ((pk ? 0 : a256(4 * 3 * nc)) + a256(4 * nc)) + (want_mat ? a256(nf) : 0); }      // (packed: the index streams alone)
   }
   int rc;
   if ((rc = uvol_ensure(ctx, T->files, ftot + 64))) return rc;
@@ -1185,8 +1216,14 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
       if (P.layout == UVOL_POINTS_INTERLEAVED) { W.o_val[0] = !P.pos ? nullptr : (out_dev ? P.pos : sv); W.o_val[1] = W.o_val[2] = nullptr; }
       else { W.o_val[0] = !P.pos ? nullptr : (out_dev ? P.pos : sv); W.o_val[1] = !P.uv ? nullptr : (out_dev ? P.uv : sv + 6 * nc); W.o_val[2] = !P.nrm ? nullptr : (out_dev ? P.nrm : sv + 3 * nc); }
     }
+    if (pk) {
+      const uvol_packed_points &P = pk[i]; GDWeldJob &W = J.w;
+      W.on = 1; W.packed = 1; W.mat_dec = -1; W.layout = UVOL_POINTS_INTERLEAVED; W.cap = (uint32_t)std::min(P.cap_points, nc); W.np = 0;
+      W.o_index = !P.index ? nullptr : (out_dev ? P.index : stg.index);
+      W.o_val[0] = !P.records ? nullptr : (out_dev ? (float *)P.records : (float *)stg.vals); W.o_val[1] = W.o_val[2] = nullptr;
+    }
     uint8_t *ob = (uint8_t *)T->outs.p + ooff[i]; size_t oo = 0;
-    for (int k = 0; k < 3; k++) { J.o_val[k] = (float *)(ob + oo); oo += a256(4 * 3 * nc); J.o_idx[k] = (uint32_t *)(ob + oo); oo += a256(4 * nc); }
+    for (int k = 0; k < 3; k++) { if (pk) J.o_val[k] = nullptr; else { J.o_val[k] = (float *)(ob + oo); oo += a256(4 * 3 * nc); } J.o_idx[k] = (uint32_t *)(ob + oo); oo += a256(4 * nc); }
     J.o_mat = want_mat ? ob + oo : nullptr; J.o_has_mat = 0;
   }
   { const int rcu = uvol_upload_staged(ctx, (uint8_t *)T->files.p, ups); if (rcu != UVOL_OK) return rcu; }
@@ -1239,10 +1276,12 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GLAUNCH(k_gdec_normals, dim3(bc, N, GD_MAXDEC), dim3(UVOL_BLOCK), 0, dj, gj);
     GLAUNCH(k_gdec_uvgeo, dim3(bc, N, GD_MAXDEC), dim3(UVOL_BLOCK), 0, dj, gj);
     GLAUNCH(k_gdec_pred, dim3(N, GD_MAXDEC), dim3(64), 0, dj, gj, 1); }
-  { uvol_ctx::Scope sc(ctx, "geodec.k8_finish", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj);
+  if (pk) { uvol_ctx::Scope sc(ctx, "geodec.k8_keys_packed", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj); }      // o_val is null: the index streams (the weld's keys) and nothing else
+  else { uvol_ctx::Scope sc(ctx, "geodec.k8_finish", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj);
     if (want_mat) GLAUNCH(k_gdec_facemat, dim3(uvol_blocks(max_nf), N), dim3(UVOL_BLOCK), 0, dj, gj); }
-  if (pts) { uvol_ctx::Scope sc(ctx, "geodec.k9_weld", 0);
+  if (pts || pk) { uvol_ctx::Scope sc(ctx, pk ? "geodec.k9_weld_packed" : "geodec.k9_weld", 0);
     const unsigned bp = uvol_blocks((size_t)3 * max_nf + 4);                 // position entries <= ecap <= corners + 3
+    if (pk) GLAUNCH(k_weld_packed_check, dim3(N), dim3(64), 0, dj);
     GLAUNCH(k_weld_clear, dim3(bp, N), dim3(UVOL_BLOCK), 0, dj);
     GLAUNCH(k_weld_count, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj);
     GLAUNCH(k_weld_scan, dim3(bp, N), dim3(UVOL_BLOCK), 0, dj);
@@ -1250,7 +1289,8 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GLAUNCH(k_weld_scatter, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj);
     GLAUNCH(k_weld_rep, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj);
     GLAUNCH(k_weld_sums, dim3(1, N), dim3(UVOL_BLOCK), 0, dj, 1);
-    GLAUNCH(k_weld_write, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj); }
+    if (pk) GLAUNCH(k_weld_write_packed, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj, gj);
+    else GLAUNCH(k_weld_write, dim3(bc, N), dim3(UVOL_BLOCK), 0, dj); }
   UVOL_HIP_CHECK(ctx, hipGetLastError());
   UVOL_HIP_CHECK(ctx, hipMemcpyAsync(T->hjobs.data(), dj, sizeof(GeoDecJob) * (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1264,10 +1304,31 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     const GeoDecJob &J = T->hjobs[i]; uvol_decoded_mesh &M = out[i];
     if (has_mat) has_mat[i] = 0;
     if (!full && J.status == GD_E_WS_OVERFLOW) { retry.push_back(i); if (status) status[i] = UVOL_OK; continue; }      // decoded again below, alone, with worst-case sizes
-    const int st = J.status == 0 ? UVOL_OK : (J.status == GW_E_FAN ? UVOL_E_UNSUPPORTED : UVOL_E_ENCODE);
+    const bool pk_refused = J.status == GW_E_PK_POS || J.status == GW_E_PK_UV || J.status == GW_E_PK_NRM;
+    const int st = J.status == 0 ? UVOL_OK : (J.status == GW_E_FAN || pk_refused ? UVOL_E_UNSUPPORTED : UVOL_E_ENCODE);
     if (status) status[i] = st;
+    if (pk_refused) {
+      const int w = J.status == GW_E_PK_POS ? 0 : J.status == GW_E_PK_UV ? 1 : 2; const GDAtt &A = J.att[J.o_dec[w]];
+      static const char *const nm[3] = { "position", "tex-coord", "normal" };
+      if (w == 2) ctx->set_error("frame %d: the normal attribute is neither octahedral nor of 3 components (%d): no packed record holds it", i, A.ncomp);
+      else if (A.seq_type != 2) ctx->set_error("frame %d: the %s attribute is not quantised (encoding %d): packed records hold the file's integers", i, nm[w], A.seq_type);
+      else ctx->set_error("frame %d: the %s attribute has %d components quantised to %d bits: packed records hold %d of at most 16 bits", i, nm[w], A.ncomp, A.qbits, w == 0 ? 3 : 2);
+      worst = st; continue;
+    }
     if (st != UVOL_OK) { ctx->set_error("frame %d: corrupt or unsupported .drc (device status %d)", i, J.status); worst = st; continue; }
     M.n_faces = (uint32_t)J.nf;
+    if (pk) {
+      uvol_packed_points &P = pk[i]; const GDWeldJob &W = J.w;
+      P.n_faces = (uint32_t)J.nf; P.n_points = W.np; P.has_uv = J.o_n[1] ? 1u : 0u; P.has_nrm = J.o_n[2] ? 1u : 0u; P.has_material = W.mat_dec >= 0 ? 1u : 0u;
+      { const GDAtt &A = J.att[J.o_dec[0]]; P.pos_bits = (uint32_t)A.qbits; for (int k = 0; k < 3; k++) P.pos_min[k] = A.minv[k]; P.pos_scale = gd_delta(A); }
+      if (P.has_uv) { const GDAtt &A = J.att[J.o_dec[1]]; P.uv_bits = (uint32_t)A.qbits; for (int k = 0; k < 2; k++) P.uv_min[k] = A.minv[k]; P.uv_scale = gd_delta(A); }
+      if (W.np > W.cap) { if (status) status[i] = UVOL_E_NOSPACE; worst = UVOL_E_NOSPACE; ctx->set_error("frame %d: %u points, capacity %zu", i, W.np, P.cap_points); continue; }
+      if (!out_dev) {
+        if (P.index) dns.push_back(UvolDnItem{ W.o_index, P.index, (size_t)J.nf * 3 * 4 });
+        if (P.records) dns.push_back(UvolDnItem{ W.o_val[0], P.records, 16 * (size_t)W.np });
+      }
+      continue;
+    }
     if (pts) {
       uvol_decoded_points &P = pts[i]; const GDWeldJob &W = J.w; const size_t np = W.np;
       P.n_faces = (uint32_t)J.nf; P.n_points = W.np; P.has_uv = J.o_n[1] ? 1u : 0u; P.has_nrm = J.o_n[2] ? 1u : 0u;
@@ -1307,7 +1368,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
   ctx->resolve_profile();
   for (int i : retry) {                                   // frames the compact workspace could not hold (more entries per face than usual)
     int st1 = UVOL_OK;
-    const int rc1 = geo_decode_batch_impl(ctx, files + i, lens + i, 1, out + i, &st1, true, out_dev, fmat ? fmat + i : nullptr, has_mat ? has_mat + i : nullptr, pts ? pts + i : nullptr);
+    const int rc1 = geo_decode_batch_impl(ctx, files + i, lens + i, 1, out + i, &st1, true, out_dev, fmat ? fmat + i : nullptr, has_mat ? has_mat + i : nullptr, pts ? pts + i : nullptr, pk ? pk + i : nullptr);
     if (rc1 != UVOL_OK) return rc1;
     if (status) status[i] = st1;
     if (st1 != UVOL_OK) worst = st1;

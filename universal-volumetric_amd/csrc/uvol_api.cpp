@@ -457,6 +457,38 @@ int uvol_decode_mesh_batch_points(uvol_ctx *ctx, const uint8_t *const *drc, cons
   }
   return status ? UVOL_OK : worst;
 }
+int uvol_decode_mesh_batch_packed(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
+                                  uvol_packed_points *out, int *status) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx || !drc || !lens || n < 0 || !out) return UVOL_E_INVALID;
+  for (int i = 0; i < n; i++)
+    if (outputs_on_device && ((uintptr_t)out[i].records & 15)) { ctx->set_error("frame %d: the device records buffer must be 16-byte aligned", i); return UVOL_E_INVALID; }      // (host outputs are staged and copied)
+  (void)hipSetDevice(ctx->device);
+  // foreign files and frames whose index array is too small fail in their own slot; the others go to the decoder in groups of max_batch
+  std::vector<int> sel; sel.reserve((size_t)n);
+  int worst = UVOL_OK;
+  for (int i = 0; i < n; i++) {
+    uvol_packed_points &P = out[i];
+    P.n_faces = P.n_points = P.has_uv = P.has_nrm = P.has_material = P.pos_bits = P.uv_bits = 0;
+    P.pos_min[0] = P.pos_min[1] = P.pos_min[2] = P.pos_scale = P.uv_min[0] = P.uv_min[1] = P.uv_scale = 0.0f;
+    uint32_t nf = 0, mv = 0; int st = UVOL_OK;
+    if (uvol_drc_info(drc[i], lens[i], &nf, &mv) != UVOL_OK) { st = UVOL_E_INVALID; ctx->set_error("frame %d: not a Draco 2.2 mesh", i); }
+    else if (P.cap_faces < nf) { st = UVOL_E_NOSPACE; P.n_faces = nf; ctx->set_error("frame %d: %u faces, capacity %u", i, nf, P.cap_faces); }
+    if (status) status[i] = st;
+    if (st == UVOL_OK) sel.push_back(i); else worst = st;
+  }
+  const int mb = ctx->prm.max_batch;
+  std::vector<const uint8_t *> f; std::vector<size_t> l; std::vector<uvol_packed_points> p; std::vector<int> s;
+  for (size_t b0 = 0; b0 < sel.size(); b0 += (size_t)mb) {
+    const int nb = (int)std::min(sel.size() - b0, (size_t)mb);
+    f.resize((size_t)nb); l.resize((size_t)nb); p.resize((size_t)nb); s.assign((size_t)nb, UVOL_OK);
+    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; f[(size_t)k] = drc[i]; l[(size_t)k] = lens[i]; p[(size_t)k] = out[i]; }
+    const int rc = geo_decode_packed(ctx, f.data(), l.data(), nb, p.data(), s.data(), outputs_on_device != 0);
+    if (rc != UVOL_OK) return rc;
+    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; out[i] = p[(size_t)k]; if (status) status[i] = s[(size_t)k]; if (s[(size_t)k] != UVOL_OK) worst = s[(size_t)k]; }
+  }
+  return status ? UVOL_OK : worst;
+}
 int uvol_parse_obj_batch_dev_mat(uvol_ctx *ctx, const uint8_t *const *obj_text, const size_t *lens, int n, int slot, uvol_mesh *meshes_out,
                                  const uint8_t **face_material_dev_out, int *status) {
   UVOL_AFTER_ASYNC(ctx);

@@ -249,6 +249,8 @@ int geo_decode_batch(uvol_ctx *ctx, const uint8_t *const *files, const size_t *l
                      uint8_t *const *face_material = nullptr, int *has_material = nullptr);
 // uvol_decode_mesh_batch_points: decode + weld (geo_weld.hpp); every file passed the header check, frames fail alone through status[]
 int geo_decode_points(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_decoded_points *pts, int *status, bool outputs_on_device);
+// uvol_decode_mesh_batch_packed: decode (index streams only) + weld into 16-byte integer records
+int geo_decode_packed(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uvol_packed_points *pk, int *status, bool outputs_on_device);
 int texdec_create(uvol_ctx *ctx);
 void texdec_destroy(uvol_ctx *ctx);
 int tex_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uint8_t *const *rgba, size_t layer_cap, bool outputs_on_device, int target, int *status = nullptr);

@@ -29,6 +29,24 @@ class DecodedPoints(C.Structure):
 UVOL_POINTS_PLANAR, UVOL_POINTS_INTERLEAVED = 0, 1
 
 
+class PackedPoints(C.Structure):
+    """uvol_packed_points: the render-ready form in 16-byte records of the file's own integers, with material ids."""
+    _fields_ = [("cap_faces", C.c_uint32), ("cap_points", C.c_size_t), ("records", C.c_void_p), ("index", C.c_void_p),
+                ("n_faces", C.c_uint32), ("n_points", C.c_uint32), ("has_uv", C.c_uint32), ("has_nrm", C.c_uint32), ("has_material", C.c_uint32),
+                ("pos_bits", C.c_uint32), ("uv_bits", C.c_uint32), ("pos_min", C.c_float * 3), ("pos_scale", C.c_float), ("uv_min", C.c_float * 2), ("uv_scale", C.c_float)]
+
+
+# one record of uvol_decode_mesh_batch_packed (16 bytes, little endian)
+PACKED_RECORD = np.dtype([("pos", "<u2", 3), ("material", "<u2"), ("uv", "<u2", 2), ("nrm", "i1", 4)])
+
+
+def packed_meta(m):
+    """The output fields of one PackedPoints as a dict (counts, flags, the dequantisation transform as float32)."""
+    return dict(n_faces=m.n_faces, n_points=m.n_points, has_uv=bool(m.has_uv), has_nrm=bool(m.has_nrm), has_material=bool(m.has_material),
+                pos_bits=m.pos_bits, uv_bits=m.uv_bits, pos_min=np.array(m.pos_min[:], np.float32), pos_scale=np.float32(m.pos_scale),
+                uv_min=np.array(m.uv_min[:], np.float32), uv_scale=np.float32(m.uv_scale))
+
+
 class Params(C.Structure):
     """project-config.json numeric fields used on the hot path (scripts/Encoder.py:171-179)."""
     _fields_ = [("Q_POSITION_ATTR", C.c_int32), ("Q_TEXTURE_ATTR", C.c_int32), ("Q_NORMAL_ATTR", C.c_int32),
@@ -51,7 +69,7 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_profile_get", "uvol_encode_texture_segments_st", "uvol_transcode_texture_segments_st",
            "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status",
            "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat",
-           "uvol_decode_mesh_batch_points"]
+           "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed"]
 
 
 def load(path=None):
@@ -79,6 +97,8 @@ def load(path=None):
                                              C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int)]
     if hasattr(L, "uvol_decode_mesh_batch_points"):      # (a build that predates the entry point still loads: tools/points_timing.py times one beside this build)
         L.uvol_decode_mesh_batch_points.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(DecodedPoints), C.POINTER(C.c_int)]
+    if hasattr(L, "uvol_decode_mesh_batch_packed"):      # (the same: tools/points_timing.py loads the parent build beside this one)
+        L.uvol_decode_mesh_batch_packed.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(PackedPoints), C.POINTER(C.c_int)]
     L.uvol_parse_obj_batch_dev_mat.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_void_p), C.POINTER(C.c_int)]
     L.uvol_texture_bound.argtypes = [C.c_uint32, C.c_uint32, C.c_int]; L.uvol_texture_bound.restype = C.c_size_t
     for nm in ("uvol_encode_texture_segment", "uvol_encode_texture_segment_dev"):
@@ -747,6 +767,51 @@ class Codec:
             else:
                 r["pos"] = a["pos"][:npnt]; r["uv"] = a["uv"][:npnt] if m.has_uv else None; r["nrm"] = a["nrm"][:npnt] if m.has_nrm else None
             res.append(r)
+        return res
+
+    def decode_mesh_batch_packed(self, files, on_device=False, arena=None, raise_on_error=True, metas=None, status_out=None):
+        """files: list of .drc bytes -> per frame the packed render-ready form (uvol_decode_mesh_batch_packed): a dict {records [n] PACKED_RECORD
+        (uint16 pos[3], uint16 material, uint16 uv[2], int8 nrm[4]: the file's quantised integers, the normal times 127 rounded), index
+        [3*faces] uint32 point per corner, n_faces, n_points, has_uv, has_nrm, has_material, pos_bits, uv_bits, pos_min [3], pos_scale, uv_min
+        [2], uv_scale (float32: value = min + q * scale, product rounded before the sum)}.  Points and index are those of
+        decode_mesh_batch_points.  The other arguments are those of decode_mesh_batch_points, `metas` a (PackedPoints * n) array; a
+        PinnedArena of points_arena_bytes(files) is large enough."""
+        files = [bytes(f) for f in files]; n = len(files)
+        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
+        if on_device:
+            if metas is None:
+                raise UvolError("decode_mesh_batch_packed(on_device=True) takes the caller's device buffers in `metas`")
+            rc = self.L.uvol_decode_mesh_batch_packed(self.h, fp, ln, n, 1, metas, st)
+            if rc != UVOL_OK:
+                raise UvolError(f"decode_mesh_batch_packed rc={rc}: {self.error()}")
+            return list(st)
+        own = metas is None
+        if own:
+            metas = (PackedPoints * n)()
+        mk = (lambda shape, dt: arena.take(shape, dt)) if arena is not None else (lambda shape, dt: np.empty(shape, dt))
+        keep = []
+        for i, f in enumerate(files):
+            m = metas[i]
+            if own:
+                nf, mv = C.c_uint32(), C.c_uint32()
+                ok = self.L.uvol_drc_info(f, len(f), C.byref(nf), C.byref(mv)) == UVOL_OK      # (a foreign file fails in its own slot below)
+                m.cap_faces = nf.value if ok else 0; m.cap_points = mv.value if ok else 0
+            cp, cf = max(1, int(m.cap_points)), max(1, int(m.cap_faces))
+            a = dict(index=mk((3 * cf,), np.uint32), records=mk((cp, 16), np.uint8))
+            m.records = a["records"].ctypes.data; m.index = a["index"].ctypes.data
+            keep.append(a)
+        rc = self.L.uvol_decode_mesh_batch_packed(self.h, fp, ln, n, 0, metas, st)
+        if status_out is not None:
+            status_out[:] = list(st)
+        if rc != UVOL_OK:
+            raise UvolError(f"decode_mesh_batch_packed rc={rc}: {self.error()}")
+        res = []
+        for i in range(n):
+            if st[i] != UVOL_OK:
+                if raise_on_error:
+                    raise UvolError(f"frame {i} failed status={st[i]}: {self.error()}")
+                res.append(None); continue
+            res.append(dict(packed_meta(metas[i]), index=keep[i]["index"][:3 * metas[i].n_faces], records=keep[i]["records"][:metas[i].n_points].view(PACKED_RECORD).reshape(-1)))
         return res
 
     # ---- measurement ----
