@@ -70,6 +70,7 @@ struct GeoLane {
   std::vector<uvol_mesh> meshes; std::vector<uint8_t *> outp; std::vector<size_t> caps;
   std::vector<const uint8_t *> mats; int frame0 = 0;      // material ids per frame (nullptr: none; empty: no frame has any); index of the group's first frame in its call
   size_t *out_lens = nullptr; int *status = nullptr; int n = 0, n_conc = 0;
+  bool late_join = false;  // the group in flight joins its auxiliary stream behind the traversals (geo_submit_impl)
   // GPU-resident form (uvol_encode_mesh_batch_dev_out): the packed output area is the CALLER's device buffer and the payload is not copied out
   uint8_t *ext_out = nullptr; size_t ext_cap = 0; size_t *ext_offs = nullptr; hipStream_t producer = nullptr; hipEvent_t ev_prod = nullptr;
   std::chrono::steady_clock::time_point t_enter; double t_prep = 0, t_enq = 0;
@@ -162,9 +163,17 @@ inline uint32_t pow2_at_least(uint64_t v) { uint32_t c = 16; while (c < v) c <<=
 // Per-vertex / per-entry arrays are sized for `ecap` entries (1.5 x the largest input attribute + slack) instead of the
 // worst case 3 * faces; a mesh that needs more (non-manifold fans, every corner its own vertex) fails with GEO_E_WS_OVERFLOW
 // on the device and is re-encoded alone with worst-case sizes (geo_encode_batch), so the compact layout never costs correctness.
-// Phases (main stream order; the auxiliary stream runs events / valence replay / context scatter between PH_FTIME and PH_HIST):
+// Phases (main stream order; the auxiliary stream runs valence replay / context scatter from PH_FTIME to its join: before PH_DENSE1 or
+// behind PH_TRAV, geo_submit_impl):
 enum { PH_DEDUP = 0, PH_FACES, PH_CT, PH_FANS0, PH_DENSE0, PH_WALK, PH_FTIME, PH_RENUM, PH_SEAMS, PH_DENSE1, PH_TRAV, PH_V2D, PH_QUANT,
        PH_PRED, PH_HIST, PH_ENT, PH_LAYOUT, PH_PINNED = -1 };
+
+// Phase after which a LATE join of the auxiliary stream sits on the main stream (geo_submit_impl): right behind the traversal launch.  The
+// replay (~50 ms) is long done when the traversals (100 - 200 ms) end, so any place up to k_hist costs the same time, and this one is
+// where the planner's total is smallest: a 200 k-face frame of a large batch (compact layout, per-face records) holds 29.2 MB with the
+// early join, about 34 MB with the late join here, 35.7 MB behind k_v2d and 36.0 MB before k_hist (the entries' order and inverse maps,
+// then the symbol arrays, would have to keep clear of the replay's inputs too).
+constexpr int GEO_LATE_JOIN_PHASE = PH_TRAV;
 
 // Collects the arrays of job J (sizes from its input counts) and sets the capacities stored in J.  full = worst-case sizes.
 // fmt0 / fmtT: record format of the walk table / of the three traversal tables (pack_face_records: 0, 1, 2)
@@ -244,7 +253,7 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
     J.he_nb = J.he_vpb ? (J.n_pos + vpb - 1) / vpb : 0u; J.he_nblk = J.he_vpb ? (uint32_t)((nc + HE_TILE - 1) / HE_TILE) : 0u;
     if (J.he_vpb) { CARVE(J.he_part, uint32_t, 3 * nc + 4, PH_CT, PH_CT); CARVE(J.he_cnt, uint32_t, (size_t)J.he_nb * J.he_nblk + 2, PH_CT, PH_CT); }
   }
-  const int aux_last = J.late_join ? PH_PRED : PH_SEAMS;            // what the auxiliary stream (valence replay, context scatter) reads lives until its join
+  const int aux_last = J.late_join ? GEO_LATE_JOIN_PHASE : PH_SEAMS;            // what the auxiliary stream (valence replay, context scatter) reads lives until its join
   CARVE(J.opp, int32_t, nc + 3, PH_CT, PH_PRED);
   CARVE(J.vert, int32_t, nc + 3, PH_FANS0, PH_PRED);
   // ---- K4 ----
@@ -262,7 +271,7 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
   CARVE(J.proc, int32_t, nfi + 1, PH_WALK, aux_last); CARVE(J.symb, uint8_t, nfi + 64, PH_WALK, aux_last);
   CARVE(J.tstart, int32_t, nfi + 1, PH_FTIME, PH_TRAV);
   CARVE(J.initc, int32_t, nfi + 1, PH_WALK, PH_FTIME); CARVE(J.stack, int32_t, fmt0 == 2 ? J.stcap + 2 : nfi + 2, PH_WALK, PH_WALK); CARVE(J.start_bits, uint8_t, nfi + 1, PH_WALK, PH_ENT);
-  // auxiliary stream (forked after PH_FTIME, joined before PH_HIST)
+  // valence replay on the auxiliary stream (behind PH_FTIME, until aux_last)
   CARVE(J.evcnt, uint8_t, nfi + 1, PH_RENUM, PH_SEAMS);
   // topology-split events: two per S symbol, a handful per mesh; worst case (retries) two per face
   J.evcap = (uint32_t)(full ? 2 * nfi + 2 : nfi / 8 + 256);
@@ -543,6 +552,7 @@ static int geo_encode_sequential(uvol_ctx *ctx, GeoJob *dj, int n, bool full, ui
 static int geo_submit(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n, int n_conc, bool on_device,
                       uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool full, GeoUp *pre = nullptr, const uint8_t *const *mats = nullptr);
 static int geo_complete(uvol_ctx *ctx, GeoLane &L);
+static inline int geo_lanes_wanted();
 
 // First half of a group of frames on lane L: lays out the workspaces, uploads host inputs, enqueues every kernel of the group and the
 // read-back of its job records.  Returns without waiting for the GPU (but for the one look at the batch's storage order, below).
@@ -564,11 +574,15 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
   // DRACO_COMPRESSION_LEVEL 0 selects sequential connectivity in stock draco_encoder (speed 10); every other level is written with the
   // level-7 tool set (valence edgebreaker)
   const bool seq = prm.draco_compression_level == 0;
-  // The valence replay is one wave per frame and takes what one frame takes (~25-50 ms); the renumber / seams group it runs beside shrinks
-  // with the batch.  Below ~1200 frames the replay is the longer of the two, so it is joined late (before the entropy stage) and
-  // overlaps the traversals too; its inputs then cannot share bytes with the record tables (+7.7 MB per frame, irrelevant at that size).
+  // The valence replay is one wave per frame and takes what one frame takes (~25-50 ms); the seams group it runs beside before the record
+  // tables of the traversals are packed is about as long at 640 frames per group and shrinks with the batch, so an early join makes the
+  // main stream wait.  So it is joined LATE, behind the traversals (which take 100 - 200 ms), wherever memory allows: its inputs then
+  // cannot share bytes with the record tables (+5 MB per 200 k-face frame; 2845 - 2900 against 2701 - 2746 frames/s at 2560 frames).
+  // Up to 1200 frames the bytes are irrelevant; a larger call joins late
+  // when the ring's lanes fit in free device memory at that size (ring_fits_late below), and early - before k_pack_tabs - otherwise.
   static const int late_env = [] { const char *e = getenv("UVOL_LATE_JOIN"); return e ? atoi(e) : -1; }();      // tests: 0 / 1 force the early / late join
-  const bool late_join = late_env >= 0 ? late_env != 0 : std::max(n, n_conc) <= 1200;      // (n_conc: the frames of the whole call are on the chip together, whatever this group's share)
+  const bool late_small = std::max(n, n_conc) <= 1200;     // (n_conc: the frames of the whole call are on the chip together, whatever this group's share)
+  bool late_join = late_env >= 0 ? late_env != 0 : late_small;
   std::vector<size_t> ws_off(n), in_off(n), zero_sz(n);
   size_t ws_total = 0, in_total = 0, out_total = 0;
   uint32_t max_nfi = 0, max_vals = 0, max_ecap = 0, he_nb_max = 0, ms_nb_max = 1; bool he_part_all = true; uint64_t algo_in = 0;
@@ -604,18 +618,53 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
   int rc;
   bool uploaded = false;
   const bool pre_up = !on_device && L.up.slot != nullptr;
+  // what the sizes and lifetimes of a frame's workspace depend on (ws_collect)
+  auto shape = [&](GeoJob &J, const uvol_mesh &m, int i, bool late) {
+    J.compact = compact ? 1 : 0;
+    J.n_pos = m.n_pos; J.nf_in = m.n_faces; J.relabel = seq ? 0 : geo_relabel_mode(); J.seq = seq ? 1 : 0; J.late_join = late ? 1 : 0;
+    J.has_uv = (m.uv && m.idx_uv && m.n_uv) ? 1 : 0; J.has_nrm = (m.nrm && m.idx_nrm && m.n_nrm) ? 1 : 0;
+    J.n_uv = J.has_uv ? m.n_uv : 0; J.n_nrm = J.has_nrm ? m.n_nrm : 0;
+    J.has_mat = (mats && mats[i]) ? 1 : 0;
+    J.qp = prm.q_position_attr; J.qt = prm.q_texture_attr; J.qn = prm.q_normal_attr;
+  };
+#ifndef HIPEMU
+  // Late join of a large call: every lane of the ring then holds this group's workspace in the late layout.  What the lanes would have to
+  // allocate beyond what they hold has to fit in free device memory with a sixteenth of the device to spare (uvol_ws_ring_fits,
+  // uvol_ws.hpp) - for the output areas and staging of lanes not yet used, the groups' size differences, and whatever else the process
+  // allocates later (a texture context's working set, the caller's next inputs): a lane that cannot get its workspace leaves the ring
+  // (lanes_cap), which costs more than the late join gains.  Once the ring has grown, nothing is left to allocate and the answer stays
+  // 'late'.  Free memory is what the DEVICE reports: memory another allocator of the process holds in reserve counts as used, so the
+  // answer depends on what the process did before its first large call, and while the ring grows the groups of one call may differ -
+  // each group is laid out for its own answer, so that costs time, never correctness.  The host cost is one cached placement look-up
+  // per frame, as in lay() below.
+  auto ring_fits_late = [&]() -> bool {
+    size_t ws = 0;
+    for (int i = 0; i < n; i++) {
+      const uvol_mesh &m = meshes[i]; if (!m.pos || !m.idx_pos || m.n_pos == 0 || m.n_faces == 0 || m.n_faces > (1u << 26)) return false;      // (lay() reports it)
+      GeoJob J{}; shape(J, m, i, true);
+      ws += layout_job(J, nullptr, full, fmt0, fmtT, G->plan, G->items).total;
+    }
+    // the lanes the call's groups go round (geo_encode_batch_begin's `want`); a call that is one group stays on its lane
+    const int ring = n_conc > n ? std::max(1, std::min(G->lanes_cap, on_device ? geo_lanes_wanted() : std::max(geo_lanes_wanted(), 4))) : 1;
+    std::vector<size_t> caps; bool self = false;
+    for (int k = 0; k < ring; k++) { const GeoLane *o = k < (int)G->lanes.size() ? G->lanes[k] : nullptr; self = self || o == &L; caps.push_back(o ? o->slab.cap : 0); }
+    if (!self) caps.push_back(L.slab.cap);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return uvol_ws_ring_fits(ws, caps, free_b, total_b);
+  };
+  if (late_env < 0 && !late_small && !seq) late_join = ring_fits_late();
+#endif
+  L.late_join = late_join;
   auto lay = [&]() -> int {
   L.hjobs.assign((size_t)n, GeoJob{});
   ws_total = 0; in_total = 0; out_total = 0; max_ecap = 0; he_nb_max = 0; ms_nb_max = 1; he_part_all = true; algo_in = 0;
   for (int i = 0; i < n; i++) {
     const uvol_mesh &m = meshes[i]; GeoJob &J = L.hjobs[i];
-    J.compact = compact ? 1 : 0;
     if (!m.pos || !m.idx_pos || m.n_pos == 0 || m.n_faces == 0 || m.n_faces > (1u << 26)) { ctx->set_error("mesh %d: empty or invalid", i); return UVOL_E_INVALID; }
-    J.n_pos = m.n_pos; J.nf_in = m.n_faces; J.relabel = seq ? 0 : geo_relabel_mode(); J.seq = seq ? 1 : 0; J.late_join = late_join ? 1 : 0;
-    J.has_uv = (m.uv && m.idx_uv && m.n_uv) ? 1 : 0; J.has_nrm = (m.nrm && m.idx_nrm && m.n_nrm) ? 1 : 0;
-    J.n_uv = J.has_uv ? m.n_uv : 0; J.n_nrm = J.has_nrm ? m.n_nrm : 0;
-    J.has_mat = (mats && mats[i]) ? 1 : 0; J.mat_lo = 0xffffffffu; J.mat_hi = 0;
-    J.nad = J.has_uv + J.has_nrm; J.qp = prm.q_position_attr; J.qt = prm.q_texture_attr; J.qn = prm.q_normal_attr;
+    shape(J, m, i, late_join);
+    J.mat_lo = 0xffffffffu; J.mat_hi = 0;
+    J.nad = J.has_uv + J.has_nrm;
     { int k = 0; if (J.has_uv) J.att_kind[k++] = 0; if (J.has_nrm) J.att_kind[k++] = 1; for (; k < 2; k++) J.att_kind[k] = -1; }
     const WsPlan &wp = layout_job(J, nullptr, full, fmt0, fmtT, G->plan, G->items);
     ws_off[i] = ws_total; ws_total += wp.total; zero_sz[i] = wp.zero;
@@ -849,10 +898,11 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     LAUNCH(k_face_time, dim3(bf, N), dim3(UVOL_BLOCK), dj);
   }
   // valence replay + context scatter depend only on the walk: run them on the auxiliary stream, beside
-  // renumber / seams / fans / DFS traversal on the main stream; joined again before the entropy stage.
+  // renumber / seams / fans / DFS traversal on the main stream; joined again before the record tables or behind the traversals (below).
   // The parallel kernels of the replay's preparation run on the MAIN stream, before the fork: beside the renumber / seams group they
-  // took 25 + 39 ms of the auxiliary stream's time (its workgroups wait behind the main stream's 5 M-workgroup grids), which made
-  // the auxiliary chain (125 ms) longer than the group it hides behind (70 ms) - the join below waited ~55 ms per batch.
+  // took 25 + 39 ms of the auxiliary stream's time (its workgroups wait behind the main stream's 5 M-workgroup grids).  Measured again
+  // with the late join at 2560 frames, where the auxiliary chain hides behind the traversals: on the auxiliary stream 2736 - 2794
+  // frames/s against 2791 - 2807 here ("measured and not kept").
   {
     LAUNCH(k_eb_event_flags, dim3(bf, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_scan_sums, dim3(1, N), dim3(UVOL_BLOCK), dj, (int)SCAN_EVENTS);
@@ -866,6 +916,9 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     LAUNCH_ON(L.aux, k_eb_ctx, dim3(N), dim3(64), dj);
   }
   UVOL_HIP_CHECK(ctx, hipEventRecord(L.ev_val, L.aux));
+  // (Seam flags and attribute vertices - k_seams, k_aseg_a, k_aseg_b - read the stored tables only, not the walk's output, and were
+  // tried on the auxiliary stream BESIDE the walk: slower in both forms of the join, 2632 - 2691 against 2733 - 2765 frames/s early;
+  // the walk is the chain's latency-bound link and pays for streaming neighbours.  DESIGN section 5, "measured and not kept".)
   {
     uvol_ctx::Scope sc(ctx, "geo.k4b_seams", 0);
     LAUNCH(k_seams, dim3(bf, N), dim3(UVOL_BLOCK), dj);
@@ -875,10 +928,10 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     LAUNCH(k_aseg_a, dim3(bci, N, 2), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_aseg_b, dim3(bci, N, 2), dim3(UVOL_BLOCK), dj);
   }
-  // The auxiliary stream (events / valence replay / context scatter, ~90 ms per 2160 frames) is joined HERE, not before the
-  // entropy stage: it then overlaps the renumber / seams group only (about as long), but everything it reads (old-order
-  // opposite corners and vertices, the symbol sequence, the valence scratch: 11.6 MB per frame) is dead before the three record
-  // tables of the attribute traversals are written and shares their addresses - the workspace peak drops from 63 to 52 MB.
+  // Early join (a large call whose ring would not fit in device memory otherwise): the auxiliary stream is joined HERE, not behind the
+  // traversals.  It then overlaps the renumber / seams group only (about as long), but everything it reads (old-order opposite corners and vertices, the symbol
+  // sequence, the valence scratch: 11.6 MB per frame) is dead before the three record tables of the attribute traversals are written and
+  // shares their addresses - the workspace peak drops from 63 to 52 MB.
   if (!late_join) UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, L.ev_val, 0));
   {
     if (base_shared) LAUNCH(k_pack_tabs, dim3(bf, N, 2), dim3(UVOL_BLOCK), dj, fmtT, 2); else LAUNCH(k_pack_tabs, dim3(bf, N, 3), dim3(UVOL_BLOCK), dj, fmtT, 1);
@@ -894,6 +947,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     if (w_trav_env && wp_trav.simt_w) wp_trav.simt_w = w_trav_env;
     launch_traversals(ctx, dj, n, wp_trav, fmtT, base_shared ? 1 : 0);
   }
+  if (late_join) UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, L.ev_val, 0));      // (GEO_LATE_JOIN_PHASE: what is born from k_v2d on may lie where the replay's inputs were)
   { uvol_ctx::Scope sc(ctx, "geo.k5b_v2d", 0); LAUNCH(k_v2d, dim3(be, N, 3), dim3(UVOL_BLOCK), dj, fmtT); }      // (own scope: geo.k5_traverse is exactly the traversal kernel, as rocprof lists it)
   {
     uvol_ctx::Scope sc(ctx, "geo.k6_predict", 0);
@@ -909,7 +963,6 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     LAUNCH(k_pred_nrm, dim3(be, N), dim3(UVOL_BLOCK), dj);
     if (any_mat) LAUNCH(k_pred_mat, dim3(be, N), dim3(UVOL_BLOCK), dj);
   }
-  if (late_join) UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, L.ev_val, 0));
   {
     uvol_ctx::Scope sc0(ctx, "geo.k7_hist_tables", 0);
     // (a group without materials does not launch the material stream's - empty - row of workgroups)
@@ -961,7 +1014,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
 static int geo_complete_impl(uvol_ctx *ctx, GeoLane &L) {
   static const bool timing = [] { const char *e = getenv("UVOL_TIMING"); return e && *e == '1'; }();       // diagnostic: host-side phases of a batch on stderr
   auto ms_since = [](std::chrono::steady_clock::time_point a) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - a).count(); };
-  const int n = L.n; const bool full = L.full, on_device = L.on_device;
+  const int n = L.n; const bool full = L.full, on_device = L.on_device, late_join = L.late_join;
   uint8_t *const *outs = L.outp.data(); size_t *out_lens = L.out_lens; int *status = L.status;
   const auto t_enter = L.t_enter; const double t_prep = L.t_prep, t_enq = L.t_enq;
   UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
@@ -1030,7 +1083,7 @@ static int geo_complete_impl(uvol_ctx *ctx, GeoLane &L) {
       if (st1 != UVOL_OK) worst = st1;
     }
   }
-  if (timing) fprintf(stderr, "[uvol-timing] geo group n=%d sizeof(GeoJob)=%zu: host prepared %.1f ms, enqueued %.1f, gpu done %.1f, packed d2h %.1f, copied out %.1f (enter at %.1f)\n", n, sizeof(GeoJob), t_prep, t_enq, t_gpu, t_d2h, ms_since(t_enter),
+  if (timing) fprintf(stderr, "[uvol-timing] geo group n=%d sizeof(GeoJob)=%zu %s join: host prepared %.1f ms, enqueued %.1f, gpu done %.1f, packed d2h %.1f, copied out %.1f (enter at %.1f)\n", n, sizeof(GeoJob), late_join ? "late" : "early", t_prep, t_enq, t_gpu, t_d2h, ms_since(t_enter),
                       std::chrono::duration<double, std::milli>(t_enter.time_since_epoch()).count());
   return status ? UVOL_OK : worst;
 }

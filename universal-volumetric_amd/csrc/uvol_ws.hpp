@@ -10,6 +10,20 @@
 #include <utility>
 #include <vector>
 
+// bytes a device buffer is allocated with when `bytes` are asked for (uvol_ensure): slack against re-allocation for slightly larger
+// batches; bounded: an eighth of a 100 GB workspace is frames that could be in flight
+static inline size_t uvol_ws_alloc_size(size_t bytes) { return bytes + std::min<size_t>(bytes / 8, (size_t)256 << 20) + 4096; }
+// Would every lane of a ring hold a workspace of `ws` bytes?  caps[k] = what lane k holds now (0: nothing yet, or a lane not created).
+// A lane that is too small gives its buffer back before it allocates uvol_ws_alloc_size(ws) (uvol_ensure), so the ring grows by the
+// differences; that growth has to fit in `free_b` with a sixteenth of the device (`total_b` / 16: 18 GB of 288) to spare.  A ring that
+// is large enough already fits whatever is free: nothing is allocated.
+static inline bool uvol_ws_ring_fits(size_t ws, const std::vector<size_t> &caps, size_t free_b, size_t total_b) {
+  const size_t want = uvol_ws_alloc_size(ws);
+  size_t grow = 0;
+  for (size_t c : caps) if (c < ws) grow += want - c;
+  return grow == 0 || grow + total_b / 16 <= free_b;
+}
+
 #define UVOL_WS_PINNED (-1)
 struct UvolWsItem { size_t bytes; int first, last; size_t off; };
 // -> offsets in items[].off; returns the total size, *zero = size of the zero-initialised head
