@@ -57,6 +57,7 @@ struct GeoUp { UvolUpSlot *slot = nullptr; std::vector<size_t> off; };
 struct GeoLane {
   GeoUp up;               // the group in flight reads its inputs from this uplink slot (slot == nullptr: caller's device arrays, or `inputs` below)
   hipStream_t stream = nullptr, aux = nullptr; bool own_stream = false;     // aux: valence replay runs beside renumber / seams / traversals
+  bool own_aux = false;   // aux is this lane's own stream; false: the context's shared one (GeoState::aux), which carries the replays of every lane in the order of their submission
   hipEvent_t ev_walk = nullptr, ev_val = nullptr, ev_fe = nullptr;          // ev_fe: this group's front end (dedup + corner table) is done
   uvol_devbuf slab;       // all per-job workspaces
   uvol_devbuf inputs;     // staged inputs when the caller passes host pointers
@@ -77,6 +78,7 @@ struct GeoLane {
 };
 struct GeoState {
   std::vector<GeoLane *> lanes; int next_lane = 0;
+  hipStream_t aux = nullptr;           // the lanes' shared auxiliary stream, where the queue budget has no room for one per lane (geo_ring, uvol_ws.hpp); created with the first lane, destroyed behind the last
   int lanes_cap = 1 << 20;             // lanes the ring may use: lowered when a lane could not get its workspace (three lanes of general-layout groups do not fit beside a full set of inputs), reset by uvol_trim
   hipEvent_t walk_last = nullptr;      // walk event of the group submitted last (UVOL_GEO_CHAIN=2)
   hipEvent_t fe_last = nullptr;        // front-end event of the group submitted last (the front ends of consecutive groups run one after the other)
@@ -88,7 +90,7 @@ struct GeoState {
   bool compact_ok = true;              // the last group was all clean, coherently stored frames: the next one starts in the compact layout (geo_submit_impl)
 };
 static void geo_lane_free(GeoLane *L) {
-  if (L->aux) { (void)hipStreamSynchronize(L->aux); (void)hipStreamDestroy(L->aux); }
+  if (L->aux) { (void)hipStreamSynchronize(L->aux); if (L->own_aux) (void)hipStreamDestroy(L->aux); }      // (a shared one: what it still holds of this lane's replays is done before the lane's buffers go)
   if (L->own_stream && L->stream) { (void)hipStreamSynchronize(L->stream); (void)hipStreamDestroy(L->stream); }
   for (uvol_devbuf *b : { &L->slab, &L->inputs, &L->jobs, &L->outs }) if (b->p) (void)hipFree(b->p);
   if (L->pinned) (void)hipHostFree(L->pinned);
@@ -96,17 +98,49 @@ static void geo_lane_free(GeoLane *L) {
   if (L->counts) (void)hipFree(L->counts);
   delete L;
 }
+// The ring's shape for the process's hardware-queue budget (uvol_ws.hpp: uvol_hw_queues, uvol_ring_shape), read once: UVOL_GEO_LANES /
+// UVOL_GEO_GROUPS force their values, UVOL_GEO_AUX=lane|shared the form of the auxiliary stream.
+static inline const UvolRingShape &geo_ring() {
+  static const UvolRingShape v = [] {
+    const char *l = getenv("UVOL_GEO_LANES"), *g = getenv("UVOL_GEO_GROUPS"), *a = getenv("UVOL_GEO_AUX");
+    const int lf = l ? std::max(1, atoi(l)) : 0, gf = g ? std::max(1, atoi(g)) : 0;
+    const int af = !a ? -1 : (strcmp(a, "shared") == 0 ? 1 : (strcmp(a, "lane") == 0 ? 0 : -1));
+    const UvolRingShape s = uvol_ring_shape(uvol_hw_queues(), lf, gf, af);
+    if (uvol_debug()) fprintf(stderr, "[uvol] geometry ring: %d hardware queues -> %d lanes x %d groups per call, %s auxiliary stream\n", uvol_hw_queues(), s.lanes, s.groups, s.shared_aux ? "one shared" : "per-lane");
+    return s; }();
+  return v;
+}
 // lane k of the context (created on first use; lane 0 = the context's stream)
 static GeoLane *geo_lane(uvol_ctx *ctx, int k) {
   GeoState *G = ctx->geo;
   while ((int)G->lanes.size() <= k) {
     GeoLane *L = new GeoLane();
     if (G->lanes.empty()) L->stream = ctx->stream; else { if (uvol_make_stream(ctx, &L->stream) != hipSuccess) { delete L; return nullptr; } L->own_stream = true; }
-    if (uvol_make_stream(ctx, &L->aux) != hipSuccess || hipEventCreate(&L->ev_walk) != hipSuccess || hipEventCreate(&L->ev_val) != hipSuccess ||
+    hipError_t ea = hipSuccess;
+    if (geo_ring().shared_aux) L->aux = G->aux;      // (nullptr until the first submission: geo_shared_aux)
+    else { ea = uvol_make_stream(ctx, &L->aux); L->own_aux = ea == hipSuccess; }
+    if (ea != hipSuccess || hipEventCreate(&L->ev_walk) != hipSuccess || hipEventCreate(&L->ev_val) != hipSuccess ||
         hipEventCreateWithFlags(&L->ev_fe, hipEventDisableTiming) != hipSuccess) { geo_lane_free(L); return nullptr; }
     G->lanes.push_back(L);
   }
   return G->lanes[k];
+}
+// The shared auxiliary stream is created with the first submission, BEHIND the main streams of all lanes of the ring: the runtime deals
+// streams to its hardware queues in the order of their creation (a new queue while the budget has one, then the queue with the fewest
+// streams), so the main streams take queues of their own first and the auxiliary stream takes what is left - on a budget that the ring
+// fills, a queue that one main stream holds already.  Created first it took a queue for itself and two main streams met on another
+// (profiles/r10_queue_budget.json, after_shared_first).  Where a stream lands stays the runtime's choice: the order is what the library
+// can offer, and tools/queue_budget.py on a kernel trace shows what came of it.
+static int geo_shared_aux(uvol_ctx *ctx) {
+  GeoState *G = ctx->geo;
+  if (!geo_ring().shared_aux) return UVOL_OK;
+  if (!G->aux) {
+    const int ring = std::max(1, std::min(G->lanes_cap, geo_ring().lanes));
+    if (!geo_lane(ctx, ring - 1)) { ctx->set_error("geometry lane: stream / event creation failed"); return UVOL_E_HIP; }
+    if (uvol_make_stream(ctx, &G->aux) != hipSuccess) { G->aux = nullptr; ctx->set_error("geometry ring: auxiliary stream creation failed"); return UVOL_E_HIP; }
+  }
+  for (GeoLane *L : G->lanes) if (!L->aux) L->aux = G->aux;
+  return UVOL_OK;
 }
 
 // uvol_trim: the device workspaces of every lane go back to the device (they only grow: a lane that once ran a whole 2560-frame call keeps
@@ -116,7 +150,7 @@ int geo_trim(uvol_ctx *ctx) {
   G->lanes_cap = 1 << 20;
   for (GeoLane *L : G->lanes) {
     if (L->busy) continue;
-    UVOL_HIP_CHECK(ctx, hipStreamSynchronize(L->stream)); UVOL_HIP_CHECK(ctx, hipStreamSynchronize(L->aux));
+    UVOL_HIP_CHECK(ctx, hipStreamSynchronize(L->stream)); if (L->aux) UVOL_HIP_CHECK(ctx, hipStreamSynchronize(L->aux));
     for (uvol_devbuf *b : { &L->slab, &L->inputs, &L->outs }) if (b->p) { UVOL_HIP_CHECK(ctx, hipFree(b->p)); b->p = nullptr; b->cap = 0; }
   }
   return UVOL_OK;
@@ -144,6 +178,7 @@ void geo_destroy(uvol_ctx *ctx) {
   if (!ctx->geo) return;
   GeoState *g = ctx->geo;
   for (GeoLane *L : g->lanes) geo_lane_free(L);
+  if (g->aux) { (void)hipStreamSynchronize(g->aux); (void)hipStreamDestroy(g->aux); }
   delete g; ctx->geo = nullptr;
 }
 
@@ -552,7 +587,7 @@ static int geo_encode_sequential(uvol_ctx *ctx, GeoJob *dj, int n, bool full, ui
 static int geo_submit(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n, int n_conc, bool on_device,
                       uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status, bool full, GeoUp *pre = nullptr, const uint8_t *const *mats = nullptr);
 static int geo_complete(uvol_ctx *ctx, GeoLane &L);
-static inline int geo_lanes_wanted();
+static inline int geo_lanes_wanted(bool on_device);
 
 // First half of a group of frames on lane L: lays out the workspaces, uploads host inputs, enqueues every kernel of the group and the
 // read-back of its job records.  Returns without waiting for the GPU (but for the one look at the batch's storage order, below).
@@ -645,7 +680,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
       ws += layout_job(J, nullptr, full, fmt0, fmtT, G->plan, G->items).total;
     }
     // the lanes the call's groups go round (geo_encode_batch_begin's `want`); a call that is one group stays on its lane
-    const int ring = n_conc > n ? std::max(1, std::min(G->lanes_cap, on_device ? geo_lanes_wanted() : std::max(geo_lanes_wanted(), 4))) : 1;
+    const int ring = n_conc > n ? std::max(1, std::min(G->lanes_cap, geo_lanes_wanted(on_device))) : 1;
     std::vector<size_t> caps; bool self = false;
     for (int k = 0; k < ring; k++) { const GeoLane *o = k < (int)G->lanes.size() ? G->lanes[k] : nullptr; self = self || o == &L; caps.push_back(o ? o->slab.cap : 0); }
     if (!self) caps.push_back(L.slab.cap);
@@ -1096,9 +1131,10 @@ static int geo_submit(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n,
   L.meshes.assign(meshes, meshes + n); L.outp.assign(outs, outs + n); L.caps.assign(caps, caps + n);
   L.out_lens = out_lens; L.status = status; L.n = n; L.n_conc = n_conc; L.on_device = on_device; L.full = full;
   hipStream_t saved = ctx->stream; ctx->stream = L.stream;
-  const int rc = geo_submit_impl(ctx, L, L.meshes.data(), n, n_conc, on_device, L.caps.data(), full);
+  int rc = geo_shared_aux(ctx);
+  if (rc == UVOL_OK) rc = geo_submit_impl(ctx, L, L.meshes.data(), n, n_conc, on_device, L.caps.data(), full);
   ctx->stream = saved;
-  if (rc != UVOL_OK && L.up.slot) { (void)hipStreamSynchronize(L.stream); (void)hipStreamSynchronize(L.aux); L.up.slot = nullptr; }      // (kernels already enqueued may read the slot: its release was never recorded)
+  if (rc != UVOL_OK && L.up.slot) { (void)hipStreamSynchronize(L.stream); if (L.aux) (void)hipStreamSynchronize(L.aux); L.up.slot = nullptr; }      // (kernels already enqueued may read the slot: its release was never recorded)
   L.busy = rc == UVOL_OK;
   return rc;
 }
@@ -1133,7 +1169,12 @@ int geo_flush(uvol_ctx *ctx) {
 // frames per call, frames/s geometry alone / beside the texture context: 2 lanes x 2 groups 4035 / 3118 - 3161, 3 x 2 4964 / 3263 - 3397, 6 x 4
 // 5307 / 3525 - 3650, 7 x 4 - / 3743 (244 GB of HBM in use), 8 x 5 5435 / 3583, 12 x 8 - / 3194 (profiles/r05_frames_in_flight.json,
 // r05_ring_shapes.json).  A lane that cannot get its workspace leaves the ring (GeoState::lanes_cap).
-static inline int geo_lanes_wanted() { static const int v = [] { const char *e = getenv("UVOL_GEO_LANES"); const int k = e ? atoi(e) : 6; return k < 1 ? 1 : (k > 16 ? 16 : k); }(); return v; }
+// Round 10: that shape needs a hardware queue per stream - thirteen with the texture context's.  On the runtime's default of four, streams share
+// queues and run one after the other: the ring follows the budget (geo_ring: fewer lanes of larger groups, one auxiliary stream for all).
+// host inputs: four groups at least under a forced lane count, as before (a group uploads while the groups before it encode; the first group's
+// upload is the only one nothing hides); the ring a queue budget gives is taken as it is.  (The auxiliary form was decided for the FORCED count,
+// uvol_ring_shape: UVOL_GEO_LANES=2 on a budget of four gives the shared stream, and host calls then run four lanes with it.)
+static inline int geo_lanes_wanted(bool on_device) { static const bool forced = getenv("UVOL_GEO_LANES") != nullptr; const int k = geo_ring().lanes; return (on_device || !forced) ? k : std::max(k, 4); }
 // frames per group at least (UVOL_GEO_MIN_GROUP, tests: small values spread small calls over the lanes): below 2 x this a call stays one
 // group - its walkers are the whole critical path anyway
 static inline int geo_min_group() { static const int v = [] { const char *e = getenv("UVOL_GEO_MIN_GROUP"); const int k = e ? atoi(e) : 160; return k < 1 ? 1 : k; }(); return v; }
@@ -1147,14 +1188,13 @@ int geo_encode_batch_begin(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool o
   GeoState *G = ctx->geo;
   if (n <= 0) return UVOL_OK;
   { bool any = false; for (int i = 0; mats && i < n; i++) any = any || mats[i] != nullptr; if (!any) mats = nullptr; }      // (no frame has materials: the call without them)
-  // host inputs: four groups at least (a group uploads while the groups before it encode; the first group's upload is the only one nothing hides)
-  const int want = std::max(1, std::min(G->lanes_cap, on_device ? geo_lanes_wanted() : std::max(geo_lanes_wanted(), 4)));
+  const int want = std::max(1, std::min(G->lanes_cap, geo_lanes_wanted(on_device)));
   static const int split_env = [] { const char *e = getenv("UVOL_GEO_SPLIT"); return e ? atoi(e) : -1; }();      // tests / diagnostic: 1 / 0 force / forbid the split
   if (split_env >= 0) split = split_env != 0;
   // groups per call <= lanes: with device inputs a call is cut into UVOL_GEO_GROUPS (default 4) groups while the ring has `want` lanes, so
   // that consecutive enqueued calls hold want / groups calls' worth of frames on the chip (the walkers' chain is flat in the frame count:
   // throughput follows the frames in flight, profiles/r05_frames_in_flight.json) without the caller keeping more inputs resident
-  static const int groups_env = [] { const char *e = getenv("UVOL_GEO_GROUPS"); const int k = e ? atoi(e) : 4; return k < 1 ? 1 : k; }();
+  const int groups_env = geo_ring().groups;      // (UVOL_GEO_GROUPS, or what the queue budget gives)
   // Host inputs that ALL lie in uvol_host_alloc memory travel through the uplink (below): their upload does not occupy a lane, so such a call is
   // cut like a call on device inputs.  (Round 5 cut every host call into as many groups as the ring has lanes: consecutive enqueued calls then
   // met lane by lane - group g of call c + 1 waited for group g of call c - and the six groups of a call ran their walkers, then their

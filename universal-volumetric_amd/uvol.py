@@ -417,6 +417,11 @@ class Codec:
             raise UvolError(f"encode_texture_segments_dev_async rc={rc}: {self.error()}")
         self._pending = getattr(self, "_pending", []) + [("tex_views", nseg, bufs, lens, None, None, ptrs)]
 
+    def pending_status(self, k=-1):
+        """The status array (ctypes ints, one per frame) of the k-th enqueued mesh call that finish() has not completed yet: finish()
+        reports a failed frame as None only, its code stays here."""
+        return self._pending[k][4]
+
     def trim(self):
         """uvol_trim: completes the context's work and gives its geometry workspaces back to the device (streams stay)."""
         rc = self.L.uvol_trim(self.h)
