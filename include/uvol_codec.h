@@ -63,7 +63,11 @@ typedef struct uvol_params {
                                        kernels then get free CU slots before the long geometry walkers take them) */
   int32_t uastc;                    /* basisu -uastc: 1 = the texture entry points write UASTC LDR 4x4 .ktx2 files (DFD colour model 166, no
                                        supercompression; every layer an independent image) instead of ETC1S/BasisLZ; default 0 (Encoder.py:290 passes no -uastc) */
-  int32_t reserved[2];
+  int32_t material_seams;           /* 1: a frame in which two materials meet at shared vertices (an interior material seam) is written with its
+                                       material attribute as a Draco MESH_CORNER_ATTRIBUTE (seam-bit stream, corner table and traversal of its own)
+                                       instead of being refused; frames without such a seam keep their bytes.  Default 0: such a frame gets
+                                       UVOL_E_UNSUPPORTED (see "material ids" below).  Took reserved[0]: struct size and UVOL_ABI_VERSION stay */
+  int32_t reserved[1];
 } uvol_params;
 
 void uvol_params_default(uvol_params *p);
@@ -194,7 +198,19 @@ int uvol_encode_mesh_batch_dev_async(uvol_ctx *ctx, const uvol_mesh *meshes, int
  * Draco writes it while every vertex has ONE material - single-material frames, and frames whose materials follow connected components: a
  * vertex attribute on the base corner table, parallelogram prediction, wrap transform.  A frame in which two materials meet at a shared
  * vertex (an interior material seam, which Draco codes as a corner attribute with a table of its own) gets status[i] = UVOL_E_UNSUPPORTED,
- * uvol_last_error names it, and the other frames of the batch are not affected: encode that frame without materials.  With
+ * uvol_last_error names it, and the other frames of the batch are not affected: encode that frame without materials - or create the
+ * context with uvol_params.material_seams = 1.  Such a frame is then written as Draco writes an attribute with interior seams, a
+ * MESH_CORNER_ATTRIBUTE: the material's decoder row is the one above with decoder type 1 and the material's own attribute-data slot (the
+ * last one); that slot's seam stream carries one bit per interior edge - 1 where the two faces carry different ids - in the order of the
+ * other seam streams; the values are one uint8 per attribute vertex of the material's seam-cut corner table, in the depth-first traversal
+ * order of THAT table, predicted by the parallelogram rule on it (previous entry where no parallelogram is available), wrap transform over
+ * the frame's [min id, max id].  The choice is made per frame on the device: a frame without such a seam - no ids, one id, ids that follow
+ * connected components - gives the bytes it gives with material_seams = 0, and a group none of whose frames carries two ids launches
+ * nothing new.  No stock file of this shape is at hand (every recorded file of the reference has one material), so this form is not
+ * byte-pinned against stock draco_encoder, like alpha slices and -cl 0; the repository's oracle decoder, which is pinned on the recorded
+ * files for the tex-coord and normal slots, reads it generically.  A seamed frame holds more device memory while it is in flight
+ * (DESIGN.md section 3); uvol_mesh_workspace has no material argument and keeps its meaning.  The DECODE side of this library does not
+ * read the corner form yet (see uvol_decode_mesh_batch_mat below); any Draco decoder, and the repository's oracle, do.  With
  * DRACO_COMPRESSION_LEVEL 0 (sequential connectivity) a call that passes any ids is refused as a whole (UVOL_E_UNSUPPORTED).  Host ids are
  * uploaded through the library's staging buffers; uvol_encode_mesh_batch_dev_out has no such form. */
 size_t uvol_mesh_bound_mat(const uvol_mesh *m);      /* upper bound of the .drc of a frame with material ids */
@@ -356,7 +372,13 @@ int uvol_decode_mesh_batch_dev(uvol_ctx *ctx, const uint8_t *const *drc, const s
 /* As uvol_decode_mesh_batch (outputs_on_device = 0) / uvol_decode_mesh_batch_dev (1), plus the material ids: face_material (may be NULL)
  * holds n entries, face_material[i] = NULL or out[i].cap_faces bytes (host / device memory like the arrays of `out`) that receive one id per
  * face, in the face order of idx_pos; has_material[i] (may be NULL) = 1 when the file carries a GENERIC uint8 1-component vertex attribute,
- * else 0 and the buffer is left alone (a generic attribute of another shape decodes as it always did and reports no material). */
+ * else 0 and the buffer is left alone (a generic attribute of another shape decodes as it always did and reports no material).  That includes
+ * the CORNER form this encoder writes with uvol_params.material_seams = 1 for a frame with interior material seams (decoder type 1), which
+ * the decode entry points do not read yet - their rule is unchanged: the decode path builds and traverses two seam-cut tables (attribute-data
+ * slots 0 and 1).  A corner-form material in one of those slots (a frame without tex-coords or without normals) decodes like every generic
+ * attribute of another shape, has_material = 0; in slot 2 (a frame with tex-coords and normals) the file is refused as a whole, like every
+ * file with a corner attribute in a third slot (status UVOL_E_ENCODE).  Decode such frames with a Draco decoder, or encode them without the
+ * parameter. */
 int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                uvol_decoded_mesh *out, uint8_t *const *face_material, int *has_material, int *status);
 

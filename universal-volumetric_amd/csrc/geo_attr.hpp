@@ -151,7 +151,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_mat_vert(GeoJob *jobs, int pass)
 // the same neighbour-availability test, the previous entry otherwise (0 for entry 0), wrap transform over the frame's [min id, max id].
 __global__ void __launch_bounds__(UVOL_BLOCK) k_pred_mat(GeoJob *jobs) {
   JOB_OR_RETURN;
-  if (!J.has_mat) return;
+  if (!J.has_mat || (J.mat_seam && J.ms.on)) return;      // (a corner attribute: k_ms_pred)
   const uint32_t p = blockIdx.x * UVOL_BLOCK + threadIdx.x;
   if (p >= J.ne[0]) return;
   const int32_t *v2d = J.v2d[0], *vt = geo_vt(J);

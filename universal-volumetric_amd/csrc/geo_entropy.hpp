@@ -416,6 +416,7 @@ __device__ inline void rabs_encode_lane(GeoJob &J, RabsStream &B, uint32_t *lds_
 // frame runs, is what it was.  A frame without materials has no buffer for it and leaves at once.
 __device__ __attribute__((noinline)) void rabs_encode_zeros_lane(GeoJob &J, RabsStream &B, uint32_t *lds_lane) {
   if (!B.buf) return;
+  if (B.bits) { rabs_encode_lane(J, B, lds_lane); return; }      // a seamed material (uvol_params.material_seams) has real bits: the general coder, from in here so that k_entropy_simt's own text stays what it was
   const uint32_t n = B.n, p0 = 255, p = 1;
   SByteOut O; O.init(B.buf + 8, B.cap - 80, lds_lane);
   uint32_t st = 4096;

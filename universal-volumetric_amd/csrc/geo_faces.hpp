@@ -45,6 +45,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_coherence(GeoJob *jobs) {
   if (on && f < J.nf_in) {
     const uint32_t a0 = J.ipos[3 * f], a1 = J.ipos[3 * f + 1], a2 = J.ipos[3 * f + 2];
     degen = (a0 == a1 || a1 == a2 || a0 == a2) ? 1u : 0u;       // (a dropped face, as long as no two positions are equal: k_relabel_decide)
+    // uvol_params.material_seams: a frame whose ids are all equal cannot have a material seam (the rare writers store the same value)
+    if (J.ms.on && f > 0 && J.imat[f] != J.imat[0]) J.ms.multi = 1;
     if (f > 0 && J.relabel == 2) {
       const uint32_t b0 = J.ipos[3 * f - 3], b1 = J.ipos[3 * f - 2], b2 = J.ipos[3 * f - 1];
       share = (a0 == b0 || a0 == b1 || a0 == b2 || a1 == b0 || a1 == b1 || a1 == b2 || a2 == b0 || a2 == b1 || a2 == b2) ? 1u : 0u;
@@ -58,7 +60,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_coherence(GeoJob *jobs) {
   const uint32_t s1 = block_sum(share), s2 = block_sum(tight), s3 = block_sum(same), s4 = block_sum(degen);
   if (threadIdx.x == 0 && on) { if (s1) atomicAdd(&J.coh_share, s1); if (s2) atomicAdd(&J.coh_tight, s2); if (s3) atomicAdd(&J.coh_same, s3); if (s4) atomicAdd(&J.n_degen, s4); }
 }
-// per frame: relabel or not; per batch (counts[0..1]): frames that are relabelled, frames with their predecessor's connectivity
+// per frame: relabel or not; per batch (counts[0..1]): frames that are relabelled, frames with their predecessor's connectivity;
+// counts[2]: frames the compact layout cannot hold; counts[3]: frames that may have a material seam (uvol_params.material_seams)
 __global__ void __launch_bounds__(64) k_relabel_decide(GeoJob *jobs, int n, uint32_t *counts) {
   const int j = (int)(blockIdx.x * 64 + threadIdx.x);
   if (j >= n) return;
@@ -70,6 +73,7 @@ __global__ void __launch_bounds__(64) k_relabel_decide(GeoJob *jobs, int n, uint
   J.ms_nb[1] = ((J.n_pos ? J.n_pos - 1 : 0) >> J.ms_sh[1]) + 1; J.ms_nblk[1] = (J.nf_in + MS_TILE - 1) / MS_TILE;
   if (J.relabel) atomicAdd(&counts[0], 1u);
   if (J.coh_same == J.nf_in) atomicAdd(&counts[1], 1u);
+  if (J.ms.on && J.ms.multi) atomicAdd(&counts[3], 1u);
   // frames the compact layout cannot hold: relabelled ones, and ones whose stored value ids are not the caller's index arrays
   if (J.status == 0 && (J.relabel || J.n_degen || J.n_dup[0] || (J.has_uv && J.n_dup[1]) || (J.has_nrm && J.n_dup[2]))) atomicAdd(&counts[2], 1u);
 }

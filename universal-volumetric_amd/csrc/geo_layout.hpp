@@ -43,7 +43,7 @@ __global__ void __launch_bounds__(64) k_layout(GeoJob *jobs) {
   a[o++] = (uint8_t)(1 + J.nad + J.has_mat);
   a[o++] = 0xff; a[o++] = 0; a[o++] = 0;
   for (int i = 0; i < J.nad; i++) { a[o++] = (uint8_t)i; a[o++] = (uint8_t)dec_type[i]; a[o++] = 0; }
-  if (J.has_mat) { a[o++] = (uint8_t)J.nad; a[o++] = 0; a[o++] = 0; }       // material: a vertex attribute on the base table, traversal 0
+  if (J.has_mat) { a[o++] = (uint8_t)J.nad; a[o++] = (uint8_t)(J.mat_seam ? 1 : 0); a[o++] = 0; }       // material: a vertex attribute on the base table - or, with interior material seams, a corner attribute on its own slot's table -, traversal 0
   a[o++] = 1; a[o++] = 0; a[o++] = 9; a[o++] = 3; a[o++] = 0; a[o++] = 0; a[o++] = 2;
   for (int i = 0; i < J.nad; i++) {
     a[o++] = 1;

@@ -125,8 +125,12 @@ __global__ void __launch_bounds__(64) k_stream_setup(GeoJob *jobs) {
   // material attribute: one symbol per base-table entry; its seam stream is n_elig zero bits (a vertex attribute has no seams)
   J.rs[GEO_RS_MAT].n = 0;
   if (J.has_mat) {
-    if (J.mat_seam) { J.status = GEO_E_MAT_SEAM; return; }
-    J.rs[GEO_RS_MAT].n = J.ne[0]; J.rb[GEO_RB_MAT].n = J.n_elig; J.rb[GEO_RB_MAT].zeros = J.n_elig;
+    if (J.mat_seam && !J.ms.on) { J.status = GEO_E_MAT_SEAM; return; }
+    if (J.mat_seam) {                                        // corner attribute: entries of its own table; its seam stream was set up by k_ms_sb_write
+      if (!J.ms.done) { J.status = GEO_E_MAT_PASS; return; }
+      J.rs[GEO_RS_MAT].n = J.ms.ne;
+    }
+    else { J.rs[GEO_RS_MAT].n = J.ne[0]; J.rb[GEO_RB_MAT].n = J.n_elig; J.rb[GEO_RB_MAT].zeros = J.n_elig; }
   }
 }
 

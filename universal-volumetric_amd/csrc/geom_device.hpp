@@ -40,6 +40,21 @@ struct RabsStream {
   uint8_t *buf; uint32_t cap; uint32_t off, len;   // piece = buf + off
 };
 
+// Material attribute with interior seams (uvol_params.material_seams; geo_matseam.hpp): the material slot's OWN storage - nothing the walkers
+// and traversers of the other tables read is widened.  Carved only for a frame submitted with the parameter set and with ids (GeoJob::ms.on).
+struct GeoMatSeam {
+  int32_t on;                          // the parameter is set and the frame has ids
+  uint32_t multi;                      // the frame's input ids are not all equal (k_coherence): only such a frame can have a seam
+  uint32_t nseg, nverts, ne;           // segments handed out; size of the table's vertex id space; entries (attribute vertices) coded
+  uint32_t done;                       // the pass ran for this frame (k_stream_setup refuses to write a seamed frame otherwise)
+  uint8_t *fseam;                      // per stored face: bit k = the edge opposite corner k is a material seam (or a boundary)
+  uint8_t *sbpack, *sbits;             // per decoder-order face: count | bits << 2 (as GeoJob::sbpack); the seam bits, one byte each
+  uint32_t *vseam;                     // per vertex: an interior material seam touches it
+  int32_t *avert;                      // attribute vertex per corner, written for the corners of touched vertices only; from k_ms_pack on: vertex << 1 | open, every corner
+  int32_t *ropp;                       // opposite corner through the seam-cut table (k_ms_pack)
+  int32_t *order, *v2d, *stack;        // coding order (corners), its inverse by attribute vertex, the traverser's pending corners
+  uint32_t *fvis, *vvis;               // visited bits of the traversal
+};
 struct GeoJob {
   // ---- inputs (device pointers) ----
   const float *pos, *uv, *nrm;
@@ -131,17 +146,20 @@ struct GeoJob {
   const uint8_t *piece_ptr[GEO_MAXPIECES]; uint32_t piece_len[GEO_MAXPIECES], piece_off[GEO_MAXPIECES]; uint32_t n_pieces;
   uint32_t out_cap;
   uint8_t *out_pack; uint64_t out_pack_off;     // packed output area of the batch + this frame's offset in it (k_out_offsets)
+  GeoMatSeam ms;                                // (last: no field the kernels of a frame without material seams read moves)
 };
 
 // bytes the material attribute added to the job record: two stream descriptors, six pointers (imat, fmat_s, fmat, vmat, sym_mat + the
 // alignment of has_mat), mat_lo / mat_hi; tests/test_hipemu_material.py pins uvol_mesh_workspace, which leaves them out, to its earlier values
-#define GEO_JOB_MAT_BYTES (sizeof(RansStream) + sizeof(RabsStream) + 6 * sizeof(void *) + 2 * sizeof(uint32_t))
+// (+ the record of the corner form, GeoMatSeam)
+#define GEO_JOB_MAT_BYTES (sizeof(RansStream) + sizeof(RabsStream) + 6 * sizeof(void *) + 2 * sizeof(uint32_t) + sizeof(GeoMatSeam))
 #define GEO_INV (-1)
 // device status codes the host reacts to: the compact workspace / the packed output area was too small for this frame
 // (geo_encode_batch re-encodes such a frame alone with worst-case sizes)
 #define GEO_E_WS_OVERFLOW (-50)
 #define GEO_E_SLAB_FULL (-51)
 #define GEO_E_MAT_SEAM (-53)           // two material ids meet at a shared vertex (an interior material seam): the frame is refused, not retried
+#define GEO_E_MAT_PASS (-54)           // a frame with a material seam reached the stream setup without its corner-attribute pass (internal error)
 #define GEO_E_DD_OVERFLOW (-52)        // a hash bin of the partitioned dedup holds more distinct values than its LDS table: retried with the hash-table dedup
 // corner codes for the serial walkers: 4 * face + k, so that face = code >> 2 and records are indexed without a division
 __device__ __forceinline__ int code_of_corner(int c) { return c < 0 ? -1 : (((c / 3) << 2) | (c % 3)); }

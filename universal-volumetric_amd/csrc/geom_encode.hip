@@ -33,6 +33,7 @@
 #include "geo_traverse_lds.hpp"
 #include "geo_walk_simt.hpp"
 #include "geo_attr.hpp"
+#include "geo_matseam.hpp"
 #include "geo_seq.hpp"
 #include "geo_entropy.hpp"
 #include "geo_layout.hpp"
@@ -289,6 +290,7 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
     if (J.he_vpb) { CARVE(J.he_part, uint32_t, 3 * nc + 4, PH_CT, PH_CT); CARVE(J.he_cnt, uint32_t, (size_t)J.he_nb * J.he_nblk + 2, PH_CT, PH_CT); }
   }
   const int aux_last = J.late_join ? GEO_LATE_JOIN_PHASE : PH_SEAMS;            // what the auxiliary stream (valence replay, context scatter) reads lives until its join
+  const int ms_last = J.ms.on ? PH_PRED : 0;              // the material's corner-attribute pass (geo_matseam.hpp) reads the decoder's face order and the boundary flags behind the traversals
   CARVE(J.opp, int32_t, nc + 3, PH_CT, PH_PRED);
   CARVE(J.vert, int32_t, nc + 3, PH_FANS0, PH_PRED);
   // ---- K4 ----
@@ -299,12 +301,12 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
   const bool base_shared = fmt0 == 2 && fmtT == 2;
   // pending corners of the walkers on per-face records: forks that still wait for their left side - tens on a regular mesh; worst case one per face
   J.stcap = (uint32_t)(full ? nfi + 2 : nfi / 8 + 1024);
-  CARVE(J.rec[0], uint8_t, rec_size(fmt0), PH_DENSE0, base_shared ? PH_V2D : PH_WALK); CARVE(J.vopen_d[0], uint8_t, ecap, PH_FANS0, PH_DENSE1);
+  CARVE(J.rec[0], uint8_t, rec_size(fmt0), PH_DENSE0, base_shared ? PH_V2D : PH_WALK); CARVE(J.vopen_d[0], uint8_t, ecap, PH_FANS0, std::max<int>(PH_DENSE1, ms_last));
   for (int w = base_shared ? 2 : 1; w < 4; w++) CARVE(J.rec[w], uint8_t, rec_bytes, PH_DENSE1, PH_V2D);
   CARVE(J.ring_d, int32_t, ecap, PH_FANS0, PH_SEAMS);
-  CARVE(J.face_time, int32_t, nfi + 1, PH_DENSE0, std::max<int>(aux_last, PH_SEAMS));
+  CARVE(J.face_time, int32_t, nfi + 1, PH_DENSE0, std::max<int>(std::max<int>(aux_last, PH_SEAMS), ms_last));
   CARVE(J.proc, int32_t, nfi + 1, PH_WALK, aux_last); CARVE(J.symb, uint8_t, nfi + 64, PH_WALK, aux_last);
-  CARVE(J.tstart, int32_t, nfi + 1, PH_FTIME, PH_TRAV);
+  CARVE(J.tstart, int32_t, nfi + 1, PH_FTIME, std::max<int>(PH_TRAV, ms_last));
   CARVE(J.initc, int32_t, nfi + 1, PH_WALK, PH_FTIME); CARVE(J.stack, int32_t, fmt0 == 2 ? J.stcap + 2 : nfi + 2, PH_WALK, PH_WALK); CARVE(J.start_bits, uint8_t, nfi + 1, PH_WALK, PH_ENT);
   // valence replay on the auxiliary stream (behind PH_FTIME, until aux_last)
   CARVE(J.evcnt, uint8_t, nfi + 1, PH_RENUM, PH_SEAMS);
@@ -350,6 +352,13 @@ void ws_collect(GeoJob &J, bool full, int fmt0, int fmtT, std::vector<WsItem> &i
     const size_t nb = b == 0 ? nfi : ((b < 3 || b == GEO_RB_MAT) ? nc : ecap);
     B.cap = (uint32_t)(nb / 4 + nb / 8 + 256); CARVE(B.buf, uint8_t, B.cap, PH_ENT, PH_LAYOUT);
   }
+  // ---- the material attribute as a corner attribute (uvol_params.material_seams, geo_matseam.hpp): the slot's own storage ----
+  if (J.ms.on) {
+    CARVE(J.ms.vseam, uint32_t, ecap / 32 + 2, PH_PINNED, PH_PINNED); CARVE(J.ms.vvis, uint32_t, ecap / 32 + 2, PH_PINNED, PH_PINNED); CARVE(J.ms.fvis, uint32_t, nfi / 32 + 2, PH_PINNED, PH_PINNED);
+    CARVE(J.ms.fseam, uint8_t, nfi + 1, PH_PRED, PH_PRED); CARVE(J.ms.sbpack, uint8_t, nfi + 1, PH_PRED, PH_PRED); CARVE(J.ms.sbits, uint8_t, nc / 2 + 64, PH_PRED, PH_ENT);
+    CARVE(J.ms.avert, int32_t, nc + 3, PH_PRED, PH_PRED); CARVE(J.ms.ropp, int32_t, nc + 3, PH_PRED, PH_PRED); CARVE(J.ms.order, int32_t, ecap + 4, PH_PRED, PH_PRED); CARVE(J.ms.v2d, int32_t, ecap, PH_PRED, PH_PRED);
+    CARVE(J.ms.stack, int32_t, (size_t)J.stcap + 2, PH_PRED, PH_PRED);
+  }
   J.arena_cap = (uint32_t)(20 * nfi + 1024); CARVE(J.arena, uint8_t, J.arena_cap, PH_LAYOUT, PH_LAYOUT);
 #undef CARVE
 }
@@ -370,7 +379,7 @@ const WsPlan &layout_job(GeoJob &J, uint8_t *base, bool full, int fmt0, int fmtT
   ws_collect(J, full, fmt0, fmtT, items);
   auto up = [](uint32_t v, uint32_t q) { return (uint64_t)((v + (uint64_t)q - 1) / q) * q; };
   const uint64_t flags = (uint64_t)J.qp | ((uint64_t)J.qt << 8) | ((uint64_t)J.qn << 16) | ((uint64_t)full << 24) | ((uint64_t)(J.relabel != 0) << 26) |
-                         ((uint64_t)(J.seq != 0) << 27) | ((uint64_t)(J.late_join != 0) << 28) | ((uint64_t)fmt0 << 29) | ((uint64_t)fmtT << 31) | ((uint64_t)(J.compact != 0) << 33) | ((uint64_t)(J.has_mat != 0) << 34);      // everything ws_collect's sizes AND lifetimes depend on
+                         ((uint64_t)(J.seq != 0) << 27) | ((uint64_t)(J.late_join != 0) << 28) | ((uint64_t)fmt0 << 29) | ((uint64_t)fmtT << 31) | ((uint64_t)(J.compact != 0) << 33) | ((uint64_t)(J.has_mat != 0) << 34) | ((uint64_t)(J.ms.on != 0) << 35);      // everything ws_collect's sizes AND lifetimes depend on
   std::vector<uint64_t> key = { up(J.nf_in, 2048), up(J.n_pos, 1024), up(J.n_uv, 1024), up(J.n_nrm, 1024), flags, items.size(), 0 };
   auto it = C.plans.find(key);
   if (it == C.plans.end()) {
@@ -609,6 +618,10 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
   // DRACO_COMPRESSION_LEVEL 0 selects sequential connectivity in stock draco_encoder (speed 10); every other level is written with the
   // level-7 tool set (valence edgebreaker)
   const bool seq = prm.draco_compression_level == 0;
+  // uvol_params.material_seams: frames with ids carry the storage of the material's corner form (geo_matseam.hpp); whether its pass is
+  // launched at all is decided below, with the look at the group's storage order
+  const bool mseam = prm.material_seams != 0 && any_mat && !seq;
+  bool mat_pass = mseam;
   // The valence replay is one wave per frame and takes what one frame takes (~25-50 ms); the seams group it runs beside before the record
   // tables of the traversals are packed is about as long at 640 frames per group and shrinks with the batch, so an early join makes the
   // main stream wait.  So it is joined LATE, behind the traversals (which take 100 - 200 ms), wherever memory allows: its inputs then
@@ -660,6 +673,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     J.has_uv = (m.uv && m.idx_uv && m.n_uv) ? 1 : 0; J.has_nrm = (m.nrm && m.idx_nrm && m.n_nrm) ? 1 : 0;
     J.n_uv = J.has_uv ? m.n_uv : 0; J.n_nrm = J.has_nrm ? m.n_nrm : 0;
     J.has_mat = (mats && mats[i]) ? 1 : 0;
+    J.ms.on = (J.has_mat && mseam) ? 1 : 0;
     J.qp = prm.q_position_attr; J.qt = prm.q_texture_attr; J.qn = prm.q_normal_attr;
   };
 #ifndef HIPEMU
@@ -831,7 +845,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     any_relabel = relabel;
     if (relabel || NC >= 256) {
       if (!L.counts) UVOL_HIP_CHECK(ctx, hipMalloc((void **)&L.counts, 64));
-      uint32_t hc[3] = { 0, 0, 0 };
+      uint32_t hc[4] = { 0, 0, 0, 0 };
       UVOL_HIP_CHECK(ctx, hipMemsetAsync(L.counts, 0, 64, ctx->stream));
       LAUNCH(k_coherence, dim3(bf, N), dim3(UVOL_BLOCK), dj);
       LAUNCH(k_relabel_decide, dim3((N + 63) / 64), dim3(64), dj, n, L.counts);
@@ -839,6 +853,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
       UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
       any_relabel = relabel && hc[0] != 0;
       lockstep = (uint64_t)hc[1] * 10u >= (uint64_t)n * 9u;
+      mat_pass = mseam && hc[3] != 0;                          // no frame of the group carries two ids: none has a material seam, nothing new is launched
       if (compact && hc[2] != 0 && attempt == 0) {           // a frame with duplicate values, a degenerate face or an incoherent storage order: general layout, once more
         compact = false; G->compact_ok = false;
         if ((rc = lay())) return rc;
@@ -987,6 +1002,22 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
   {
     uvol_ctx::Scope sc(ctx, "geo.k6_predict", 0);
     if (any_mat) { LAUNCH(k_mat_vert, dim3(bc, N), dim3(UVOL_BLOCK), dj, 0); LAUNCH(k_mat_vert, dim3(bc, N), dim3(UVOL_BLOCK), dj, 1); }      // ids per vertex, then the seam test (k_stream_setup refuses the frame)
+    if (mat_pass) {
+      // the material attribute of the frames in which two ids meet at a vertex (mat_seam, just found), as a corner attribute: seam flags, seam
+      // bits in decoder order, attribute vertices, one traversal of the material's table, its inverse map, the residuals.  Frames without a
+      // seam leave every kernel at once.
+      uvol_ctx::Scope sm(ctx, "geo.k6b_mat_seams", 0);
+      LAUNCH(k_ms_flags, dim3(bf, N), dim3(UVOL_BLOCK), dj);
+      LAUNCH(k_ms_sb_count, dim3(bf, N), dim3(UVOL_BLOCK), dj);
+      LAUNCH(k_scan_sums, dim3(1, N), dim3(UVOL_BLOCK), dj, (int)SCAN_ELIG);
+      LAUNCH(k_ms_sb_write, dim3(bf, N), dim3(UVOL_BLOCK), dj);
+      LAUNCH(k_ms_aseg, dim3(bc, N), dim3(UVOL_BLOCK), dj, 0);
+      LAUNCH(k_ms_aseg, dim3(bc, N), dim3(UVOL_BLOCK), dj, 1);
+      LAUNCH(k_ms_pack, dim3(bf, N), dim3(UVOL_BLOCK), dj);
+      LAUNCH(k_ms_traverse, dim3(N), dim3(64), dj);
+      LAUNCH(k_ms_v2d, dim3(be, N), dim3(UVOL_BLOCK), dj);
+      LAUNCH(k_ms_pred, dim3(be, N), dim3(UVOL_BLOCK), dj);
+    }
     LAUNCH(k_stream_setup, dim3(N), dim3(64), dj);
     LAUNCH(k_pred_pos, dim3(be, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_pred_uv, dim3(be, N), dim3(UVOL_BLOCK), dj);

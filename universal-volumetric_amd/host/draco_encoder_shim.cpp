@@ -16,6 +16,8 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "-cl")) prm.draco_compression_level = std::atoi(val());
     else if (argv[i][0] == '-' && i + 1 < argc && argv[i + 1][0] != '-') ++i;          // unknown option with a value: ignored
   }
+  // UVOL_MATERIAL_SEAMS=1 (the stock driver cannot pass a flag): materials that meet at shared vertices are written as a corner attribute
+  { const char *e = std::getenv("UVOL_MATERIAL_SEAMS"); if (e && *e == '1') prm.material_seams = 1; }
   if (in.empty()) { std::fprintf(stderr, "Usage: draco_encoder -i <input.obj> -o <output.drc> [-qp -qt -qn -qg -cl]\n"); return 1; }
   if (out.empty()) out = in + ".drc";
   if (prm.draco_compression_level < 0 || prm.draco_compression_level > 10) { std::fprintf(stderr, "Error: The compression level must be in [0, 10].\n"); return 1; }
@@ -30,7 +32,7 @@ int main(int argc, char **argv) {
   if (!m.uv.empty()) { um.uv = m.uv.data(); um.n_uv = (uint32_t)m.uv.size() / 2; um.idx_uv = m.idx_uv.data(); }
   if (!m.nrm.empty()) { um.nrm = m.nrm.data(); um.n_nrm = (uint32_t)m.nrm.size() / 3; um.idx_nrm = m.idx_nrm.data(); }
   // `usemtl` lines: the GENERIC uint8 material attribute stock draco_encoder adds (uvol_encode_mesh_batch_mat).  Not at -cl 0 (sequential
-  // connectivity), and not where two materials meet at a vertex: such a file is written without the attribute, and stderr says so.
+  // connectivity), and - unless UVOL_MATERIAL_SEAMS=1 - not where two materials meet at a vertex: such a file is written without the attribute, and stderr says so.
   const uint8_t *fm = m.face_mat.empty() ? nullptr : m.face_mat.data();
   if (fm && prm.draco_compression_level == 0) { std::fprintf(stderr, "draco_encoder (uvol shim): %s: -cl 0: the material attribute (usemtl) is left out\n", in.c_str()); fm = nullptr; }
   std::vector<uint8_t> buf(fm ? uvol_mesh_bound_mat(&um) : uvol_mesh_bound(&um)); size_t len = 0;

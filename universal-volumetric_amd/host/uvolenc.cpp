@@ -3,11 +3,13 @@
 // draco_encoder / basisu once per frame / per batch.  Output layout and manifest follow what the stock
 // player reads (src/Interfaces.ts:75-132, src/V2/player.ts:141-174).
 //
-//   uvolenc project-config.json [--gpus N] [--device D] [--batch-frames F] [--ingest-threads T] [--targets ktx2[,etc2]] [--uastc] [--device-inflate [--tex-batch-frames F]]
+//   uvolenc project-config.json [--gpus N] [--device D] [--batch-frames F] [--ingest-threads T] [--targets ktx2[,etc2]] [--uastc] [--material-seams] [--device-inflate [--tex-batch-frames F]]
 //                               [--force] [--encoder-py-manifest]
 //   --targets   texture targets to write (src/Interfaces.ts:19 TextureFileFormat): `ktx2` always; `etc2` adds one raw ETC2 RGB
 //               (ETC1-subset) block image per frame, transcoded on the GPU from the ETC1S segments, and a second target in the manifest
 //   --uastc     the KTX2 files carry UASTC LDR 4x4 blocks (`basisu -uastc`) instead of ETC1S/BasisLZ
+//   --material-seams   (or UVOL_MATERIAL_SEAMS=1) frames whose `usemtl` materials meet at shared vertices are written with the material
+//               attribute as a corner attribute instead of without it
 //   --gpus N    rank r of N encodes the segment-aligned block shard_plan() gives it: whole texture segments and the
 //               geometry frames with the same indices; one host thread per GPU and stage, no data crosses between GPUs
 #include "uvol_host.hpp"
@@ -58,7 +60,8 @@ int main(int argc, char **argv) {
   }
   const auto t_start = std::chrono::steady_clock::now();
   { const char *e = std::getenv("UVOL_TIMING"); g_timing = e && *e == '1'; }
-  int n_gpus = 1, device0 = 0, frames_per_batch = 32, ingest_threads = 0; bool force = false, encpy = false, want_etc2 = false, uastc = false, host_obj = false, host_png = false, dev_inflate = false, pinned_text = false; int tex_batch_frames = 0;
+  int n_gpus = 1, device0 = 0, frames_per_batch = 32, ingest_threads = 0; bool force = false, encpy = false, want_etc2 = false, uastc = false, host_obj = false, host_png = false, dev_inflate = false, pinned_text = false, material_seams = false; int tex_batch_frames = 0;
+  { const char *e = std::getenv("UVOL_MATERIAL_SEAMS"); material_seams = e && *e == '1'; }      // (= --material-seams)
   for (int i = 2; i < argc; i++) {
     if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) n_gpus = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--device") && i + 1 < argc) device0 = std::atoi(argv[++i]);
@@ -71,6 +74,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--tex-batch-frames") && i + 1 < argc) tex_batch_frames = std::atoi(argv[++i]);      // images per texture call (default: --batch-frames)
     else if (!std::strcmp(argv[i], "--host-obj-parser")) host_obj = true;          // OBJ text parsed by the ingest threads (as until round 3) instead of on the GPU
     else if (!std::strcmp(argv[i], "--uastc")) uastc = true;
+    else if (!std::strcmp(argv[i], "--material-seams")) material_seams = true;      // frames whose materials meet at shared vertices keep their material attribute (uvol_params.material_seams)
     else if (!std::strcmp(argv[i], "--encoder-py-manifest")) encpy = true;
     else if (!std::strcmp(argv[i], "--targets") && i + 1 < argc) {
       const std::string t = argv[++i]; size_t a = 0;
@@ -97,7 +101,7 @@ int main(int argc, char **argv) {
 
   uvol_params prm; uvol_params_default(&prm);
   prm.q_position_attr = cfg.q_position; prm.q_texture_attr = cfg.q_texture; prm.q_normal_attr = cfg.q_normal; prm.q_generic_attr = cfg.q_generic;
-  prm.draco_compression_level = cfg.compression_level; prm.ktx2_batch_size = cfg.ktx2_batch_size; prm.max_batch = frames_per_batch; prm.uastc = uastc ? 1 : 0;
+  prm.draco_compression_level = cfg.compression_level; prm.ktx2_batch_size = cfg.ktx2_batch_size; prm.max_batch = frames_per_batch; prm.uastc = uastc ? 1 : 0; prm.material_seams = material_seams ? 1 : 0;
   // one geometry and one texture context (= HIP stream) per GPU: the two stages of a GPU run side by side
   // (+ one ingest context per GPU when the OBJ text is parsed on the device: contexts are independent, so batch b + 1 is parsed while the
   // geometry context's enqueued call encodes batch b)
