@@ -209,8 +209,8 @@ int uvol_encode_mesh_batch_dev_async(uvol_ctx *ctx, const uvol_mesh *meshes, int
  * nothing new.  No stock file of this shape is at hand (every recorded file of the reference has one material), so this form is not
  * byte-pinned against stock draco_encoder, like alpha slices and -cl 0; the repository's oracle decoder, which is pinned on the recorded
  * files for the tex-coord and normal slots, reads it generically.  A seamed frame holds more device memory while it is in flight
- * (DESIGN.md section 3); uvol_mesh_workspace has no material argument and keeps its meaning.  The DECODE side of this library does not
- * read the corner form yet (see uvol_decode_mesh_batch_mat below); any Draco decoder, and the repository's oracle, do.  With
+ * (DESIGN.md section 3); uvol_mesh_workspace has no material argument and keeps its meaning.  The DECODE side of this library reads the
+ * corner form in every slot (see uvol_decode_mesh_batch_mat and uvol_decode_mesh_batch_packed below), as any Draco decoder does.  With
  * DRACO_COMPRESSION_LEVEL 0 (sequential connectivity) a call that passes any ids is refused as a whole (UVOL_E_UNSUPPORTED).  Host ids are
  * uploaded through the library's staging buffers; uvol_encode_mesh_batch_dev_out has no such form. */
 size_t uvol_mesh_bound_mat(const uvol_mesh *m);      /* upper bound of the .drc of a frame with material ids */
@@ -371,14 +371,17 @@ int uvol_decode_mesh_batch_dev(uvol_ctx *ctx, const uint8_t *const *drc, const s
 
 /* As uvol_decode_mesh_batch (outputs_on_device = 0) / uvol_decode_mesh_batch_dev (1), plus the material ids: face_material (may be NULL)
  * holds n entries, face_material[i] = NULL or out[i].cap_faces bytes (host / device memory like the arrays of `out`) that receive one id per
- * face, in the face order of idx_pos; has_material[i] (may be NULL) = 1 when the file carries a GENERIC uint8 1-component vertex attribute,
- * else 0 and the buffer is left alone (a generic attribute of another shape decodes as it always did and reports no material).  That includes
- * the CORNER form this encoder writes with uvol_params.material_seams = 1 for a frame with interior material seams (decoder type 1), which
- * the decode entry points do not read yet - their rule is unchanged: the decode path builds and traverses two seam-cut tables (attribute-data
- * slots 0 and 1).  A corner-form material in one of those slots (a frame without tex-coords or without normals) decodes like every generic
- * attribute of another shape, has_material = 0; in slot 2 (a frame with tex-coords and normals) the file is refused as a whole, like every
- * file with a corner attribute in a third slot (status UVOL_E_ENCODE).  Decode such frames with a Draco decoder, or encode them without the
- * parameter. */
+ * face, in the face order of idx_pos; has_material[i] (may be NULL) = 1 when the file carries a GENERIC uint8 1-component attribute with plain
+ * integer values, either as a vertex attribute (decoder type 0, on the base corner table: what stock draco_encoder writes while no two
+ * materials meet at a vertex) or in the CORNER form (decoder type 1, on the seam-cut table of its own attribute-data slot: what this encoder
+ * writes with uvol_params.material_seams = 1 for a frame with interior material seams); else 0 and the buffer is left alone (a generic
+ * attribute of another shape decodes as it always did and reports no material).  face_material[f] is the value at corner 3 f; this encoder
+ * writes one id on all three corners of a face.  The corner form in slot 0 or 1 (a frame without tex-coords or without normals) is read off
+ * the two seam-cut tables every call builds; in slot 2 (a frame with tex-coords and normals) the material has a third table, which the calls
+ * that return materials - this one with face_material or has_material non-NULL, and uvol_decode_mesh_batch_packed - build in a pass of their
+ * own, enqueued only when a file of the call carries such an attribute (the decoder rows are looked at on the host).
+ * uvol_decode_mesh_batch, _dev and _points decode position, tex-coord and normal of such a file and skip the material's values.  Any other
+ * corner attribute in a third slot is refused as before (status UVOL_E_ENCODE). */
 int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                uvol_decoded_mesh *out, uint8_t *const *face_material, int *has_material, int *status);
 
@@ -441,9 +444,12 @@ int uvol_decode_mesh_batch_points(uvol_ctx *ctx, const uint8_t *const *drc, cons
  * which reproduces the floats of uvol_decode_mesh_batch[_points] bit for bit (the checker's drc_dequant evaluates the same expression, built
  * with floating-point contraction off; tests/test_hipemu_packed.py asserts it against NumPy).  A shader that fuses the two differs by at
  * most one unit in the last place.  pos_min / uv_min are the attribute's minimum values as the file stores them.
- * Material: the attribute uvol_decode_mesh_batch_mat reads (GENERIC uint8, one component, a vertex attribute on the base corner table of
- * an edgebreaker file), under the same condition for has_material.  Its entry is a function of the position entry, so it never splits a
- * point; `material` is its value at the point's first corner.  A generic attribute of any other shape: has_material = 0, slot zero.
+ * Material: the attribute uvol_decode_mesh_batch_mat reads (GENERIC uint8, one component, plain integers, of an edgebreaker file), under the
+ * same condition for has_material.  As a vertex attribute its entry is a function of the position entry, so it never splits a point.  As
+ * a corner attribute (interior material seams) the corner's material value is a fourth member of the point tuple: a (position, tex-coord,
+ * normal) tuple used by corners of different ids becomes one point per id, points are still numbered by first appearance in corner order
+ * and n_points <= 3 n_faces still holds; where no tuple carries two ids, index and n_points are those of uvol_decode_mesh_batch_points.
+ * `material` is the value at the point's first corner.  A generic attribute of any other shape: has_material = 0, slot zero.
  * records == NULL or index == NULL skips that output.  A DEVICE records buffer must be 16-byte aligned (one 16-byte store per point); a
  * misaligned one in any frame fails the whole call with UVOL_E_INVALID before anything runs.  Capacity and per-frame statuses as in the
  * float form: UVOL_E_NOSPACE (points or faces exceed the capacities: n_points / n_faces are the needed counts, nothing of the frame is

@@ -2,7 +2,8 @@
 // (uvol_decode_mesh_batch_points; what the stock player's DRACOLoader hands a BufferGeometry).
 // Part of the geometry decoder translation unit: included by geom_decode.hip after k_gdec_finish (not a standalone header).
 // ------------------------------------------------------------------------------------------------
-// A point is a distinct tuple (idx_pos[c], idx_uv[c], idx_nrm[c]); points are numbered by first appearance in corner order.  The keys are
+// A point is a distinct tuple (idx_pos[c], idx_uv[c], idx_nrm[c]) - on the packed path, for a frame whose material is a corner attribute, with
+// the corner's material value as a fourth member (J.w.cmat, k_m3_cornermat) -; points are numbered by first appearance in corner order.  The keys are
 // the three index streams k_gdec_finish has just written (12 bytes per corner, never copied).  Route (b) of the two that fit this code base,
 // "position fans": a point never spans two position entries, so the corners are grouped by position entry with a counting sort and every
 // corner compares itself against its own small fan (~6 corners) - nothing is hashed, the result is exact by construction and independent
@@ -13,7 +14,7 @@
 //   k_weld_scan     counters -> block-local exclusive offsets + block sums            } fan start of entry p =
 //   k_weld_sums     block sums -> block offsets (one workgroup per frame)             }   bsum_p[p / 256] + cnt[p]
 //   k_weld_scatter  fan[start + rank] = corner
-//   k_weld_rep      representative = lowest corner of the fan with equal (uv, normal) entries; first-appearance flags scanned per block
+//   k_weld_rep      representative = lowest corner of the fan with equal (uv, normal) entries (and corner material); first-appearance flags scanned per block
 //   k_weld_sums     again for the flags -> point ids, n_points
 //   k_weld_write    index[c] = point of the representative; the first corner of a point gathers its values (bit copies, no arithmetic)
 // uvol_decode_mesh_batch_packed runs the same stages up to the point ids, k_weld_packed_check ahead of them and k_weld_write_packed in
@@ -112,10 +113,11 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_weld_rep(GeoDecJob *jobs) {
   uint32_t best = c;
   if (live) {
     const uint32_t p = V.ip[c], ku = V.has_uv ? V.iu[c] : 0u, kn = V.has_nrm ? V.in[c] : 0u;
+    const uint8_t *cm = J.w.mat_corner ? J.w.cmat : nullptr; const uint32_t km = cm ? cm[c] : 0u;
     const uint32_t s = J.w.bsum_p[p / UVOL_BLOCK] + J.w.cnt[p], e = p + 1 < V.np ? J.w.bsum_p[(p + 1) / UVOL_BLOCK] + J.w.cnt[p + 1] : V.nc;
     for (uint32_t j = s; j < e; j++) {                      // <= GW_MAXFAN corners (k_weld_scan)
       const uint32_t c2 = J.w.fan[j];
-      if (c2 < best && (!V.has_uv || V.iu[c2] == ku) && (!V.has_nrm || V.in[c2] == kn)) best = c2;
+      if (c2 < best && (!V.has_uv || V.iu[c2] == ku) && (!V.has_nrm || V.in[c2] == kn) && (!cm || cm[c2] == km)) best = c2;
     }
     J.w.rep[c] = best;
   }
@@ -181,7 +183,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_weld_write_packed(GeoDecJob *job
   if (J.w.o_index) J.w.o_index[c] = id;
   if (r != c || !J.w.o_val[0]) return;
   const int32_t *pv = J.att[J.o_dec[0]].vals + 3 * (size_t)V.ip[c];
-  const uint32_t mat = J.w.mat_dec >= 0 ? (uint32_t)gd_mat_value(J, G, J.w.mat_dec, c) : 0u;
+  const uint32_t mat = J.w.mat_dec >= 0 ? (J.w.mat_corner ? (uint32_t)J.w.cmat[c] : (uint32_t)gd_mat_value(J, G, J.w.mat_dec, c)) : 0u;
   uint4 rec;
   rec.x = ((uint32_t)pv[0] & 0xffffu) | ((uint32_t)pv[1] << 16);
   rec.y = ((uint32_t)pv[2] & 0xffffu) | (mat << 16);

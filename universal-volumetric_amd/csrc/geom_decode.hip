@@ -13,6 +13,7 @@
 //   k_pack_faces / k_traverse / k_v2d  (geom_encode.hip) the SAME DepthFirstTraverser kernels the encoder uses
 //   k_gdec_rans     again for the attribute symbol streams (their lengths are the traversal results)
 //   k_gdec_pred     1 lane / (decoder, frame)   parallelogram / tex-coord-portable / geometric-normal prediction + transforms
+//   k_m3_*          uvol_decode_mesh_batch_mat / _packed only (geo_mattab_dec.hpp): a material on a third seam-cut table (attribute-data slot 2)
 //   k_gdec_finish   parallel           dequantisation (fp32, octahedral) and per-corner entry indices
 //   k_weld_*        parallel           uvol_decode_mesh_batch_points / _packed only (geo_weld.hpp): one index per corner + one value record per point
 #include "uvol_common.hpp"
@@ -27,12 +28,12 @@
 #define GD_E_WS_OVERFLOW (-50)      // the compact workspace cannot hold this frame (more entries per face than usual): retried with worst-case sizes
 
 struct GDRans { uint32_t present, scheme, bl, prec_bits, ns, max_ns, max_prec_bits, tab_off, pay_off, pay_len, nvals; uint32_t *probs, *cum, *lut, *out;
-                uint32_t early, redo; };      // attribute streams: decoded beside the traversal with the count the tables predict / decoded again after it (count differed)
+                uint32_t early, redo; };      // attribute streams: decoded beside the traversal with the count the tables predict / decoded again after it (count differed); early 3: the third table's stream (geo_mattab_dec.hpp)
 struct GDRabs { uint32_t present, p0, pay_off, pay_len; };
 struct GDAtt {
   int32_t att_data_id, dec_type, att_type, data_type, ncomp, unique_id, seq_type, pred_method, transform, nc;
   int32_t lo, hi, n_orient, maxq, cen, qbits; float minv[4], range;
-  int32_t table;                 // 0 = base corner table, 1 + i = attribute table i
+  int32_t table;                 // 0 = base corner table, 1 + i = attribute table i (3: the material's own pass, geo_mattab_dec.hpp; the shared stages skip its decoder)
   int32_t *vals;                 // ne * nc decoded integers, entry order
   GDRabs aux;                    // uv orientation bits / normal flip bits
 };
@@ -40,8 +41,16 @@ struct GDAtt {
 struct GDWeldJob {
   uint32_t on, layout, cap, np;        // layout: UVOL_POINTS_*; cap: points the value outputs hold; np: points of the frame (out)
   uint32_t packed; int32_t mat_dec;    // packed: 16-byte records of the file's integers (o_val[0] is the one buffer); mat_dec: decoder of the material attribute or -1 (out)
+  uint32_t mat_corner; uint8_t *cmat;  // packed, material as a corner attribute: the value at every corner (k_m3_cornermat) - a key of the point tuple
   uint32_t *cnt, *fan, *rep, *pid, *bsum_p, *bsum_c;
   float *o_val[3]; uint32_t *o_index;  // planar: pos / uv / nrm (any may be null); interleaved: o_val[0] is the one buffer
+};
+// third seam-cut table (attribute-data slot 2, geo_mattab_dec.hpp): storage of its own, carved for the calls that return materials; all zero for the others
+struct GDMatTab {
+  uint32_t on; int32_t dec; uint32_t ne;          // the pass is carved; decoder on table 3 or -1; entries the traversal coded
+  uint8_t *vopen; uint32_t *fvis, *vvis;          // on-boundary flag per attribute vertex; visited bits of the traversal (all start out zero)
+  int32_t *ropp, *order, *v2d, *stack, *nbr;      // opposite corner through the seam-cut table; coding order (corners), its inverse by attribute vertex; pending corners; parallelogram neighbours
+  uint32_t *probs, *cum, *lut, *syms;             // the symbol stream's tables and symbols (M3_NS / M3_PREC_BITS)
 };
 struct GeoDecJob {
   const uint8_t *file; uint32_t file_len; int32_t status;
@@ -65,23 +74,24 @@ struct GeoDecJob {
   // outputs (device): position / uv / normal values and per-corner entry indices
   float *o_val[3]; uint32_t *o_idx[3]; uint32_t o_n[3]; int32_t o_dec[3];
   GDWeldJob w;
-  uint8_t *o_mat; int32_t o_has_mat;      // material id per face (the face order of o_idx), when the file carries a GENERIC uint8 1-component vertex attribute
+  uint8_t *o_mat; int32_t o_has_mat;      // material id per face (the face order of o_idx), when the file carries a GENERIC uint8 1-component vertex or corner attribute
+  GDMatTab m3;
 };
 
-// ---- byte reader (one lane) ----
+// ---- byte reader (one lane; gdec_corner_material reads the decoder rows with it on the host) ----
 struct GRd { const uint8_t *b; uint32_t n, o; int err; };
-__device__ __forceinline__ uint32_t gr_u8(GRd &r) { if (r.o + 1 > r.n) { r.err = 1; return 0; } return r.b[r.o++]; }
-__device__ __forceinline__ int32_t gr_i32(GRd &r) { if (r.o + 4 > r.n) { r.err = 1; return 0; } uint32_t v = 0; for (int k = 0; k < 4; k++) v |= (uint32_t)r.b[r.o + k] << (8 * k); r.o += 4; return (int32_t)v; }
-__device__ __forceinline__ float gr_f32(GRd &r) { const int32_t v = gr_i32(r); float f; memcpy(&f, &v, 4); return f; }
-__device__ __forceinline__ uint32_t gr_varint(GRd &r) {
+__host__ __device__ __forceinline__ uint32_t gr_u8(GRd &r) { if (r.o + 1 > r.n) { r.err = 1; return 0; } return r.b[r.o++]; }
+__host__ __device__ __forceinline__ int32_t gr_i32(GRd &r) { if (r.o + 4 > r.n) { r.err = 1; return 0; } uint32_t v = 0; for (int k = 0; k < 4; k++) v |= (uint32_t)r.b[r.o + k] << (8 * k); r.o += 4; return (int32_t)v; }
+__host__ __device__ __forceinline__ float gr_f32(GRd &r) { const int32_t v = gr_i32(r); float f; memcpy(&f, &v, 4); return f; }
+__host__ __device__ __forceinline__ uint32_t gr_varint(GRd &r) {
   uint64_t v = 0; int s = 0;
   for (;;) { if (r.o >= r.n || s > 63) { r.err = 1; return 0; } const uint32_t c = r.b[r.o++]; v |= (uint64_t)(c & 0x7f) << s; s += 7; if (c < 0x80) break; }
   return (uint32_t)v;
 }
 // rabs section: prob byte, varint length, payload
-__device__ inline void gr_rabs(GRd &r, GDRabs &B) { B.present = 1; B.p0 = gr_u8(r); B.pay_len = gr_varint(r); B.pay_off = r.o; if (r.o + B.pay_len > r.n) r.err = 1; else r.o += B.pay_len; }
+__host__ __device__ inline void gr_rabs(GRd &r, GDRabs &B) { B.present = 1; B.p0 = gr_u8(r); B.pay_len = gr_varint(r); B.pay_off = r.o; if (r.o + B.pay_len > r.n) r.err = 1; else r.o += B.pay_len; }
 // rANS symbol section (RAW scheme): scheme, bit length, alphabet size, probability table, varint length, payload
-__device__ inline void gr_rans(GRd &r, GDRans &S, uint32_t nvals) {
+__host__ __device__ inline void gr_rans(GRd &r, GDRans &S, uint32_t nvals) {
   S.present = 1; S.nvals = nvals; S.scheme = gr_u8(r); S.bl = gr_u8(r);
   if (S.scheme != 1) { r.err = 2; return; }
   int pb = (3 * (int)S.bl) / 2; if (pb < 12) pb = 12; if (pb > 20) pb = 20; S.prec_bits = (uint32_t)pb;
@@ -185,8 +195,10 @@ __global__ void __launch_bounds__(64) k_gdec_index(GeoDecJob *jobs) {
   // attribute sections: prediction scheme, symbols, scheme data, transform data
   for (int d = 0; d < ndec; d++) {
     GDAtt &A = J.att[d];
-    if (A.dec_type == 1) { if (A.att_data_id < 0 || A.att_data_id >= nad || A.att_data_id > 1) { J.status = -23; return; } A.table = 1 + A.att_data_id; } else A.table = 0;
+    if (A.dec_type == 1) { if (A.att_data_id < 0 || A.att_data_id >= nad || A.att_data_id > 2) { J.status = -23; return; } A.table = 1 + A.att_data_id; } else A.table = 0;
     A.pred_method = (int8_t)gr_u8(r); A.transform = (int8_t)gr_u8(r);
+    // a third seam-cut table is read for the material shape alone (gd_mat_decoder's row, parallelogram or difference with the wrap transform)
+    if (A.table == 3 && !(A.att_type == 4 && A.data_type == 2 && A.ncomp == 1 && A.seq_type == 1 && (A.pred_method == 1 || A.pred_method == 0) && A.transform == 1)) { J.status = -23; return; }
     if (gr_u8(r) != 1) { J.status = -24; return; }
     A.nc = A.seq_type == 3 ? 2 : A.ncomp;
     if (A.nc < 1 || A.nc > 4) { J.status = -24; return; }
@@ -234,8 +246,8 @@ __global__ void __launch_bounds__(64) k_gdec_rans(GeoDecJob *jobs, int first, in
   // ONCE per workgroup so that all lanes take the same path to the barriers below
   __shared__ int s_err, s_go;
   // mode 0: every present stream; 1 / 3: the streams whose value count was predicted after the index / after the seam tables (early passes
-  // on the second stream); 2: the ones the early passes did not cover or whose count the traversal corrected
-  if (lane == 0) s_go = (J.status == 0 && S.present && S.nvals != 0 && (mode == 0 || (mode == 2 ? S.redo != 0 : S.early == (mode == 1 ? 1u : 2u)))) ? 1 : 0;
+  // on the second stream); 2: the ones the early passes did not cover or whose count the traversal corrected; 4: the third table's stream (k_m3_traverse)
+  if (lane == 0) s_go = (J.status == 0 && S.present && S.nvals != 0 && (mode == 0 || (mode == 2 ? S.redo != 0 : S.early == (mode == 1 ? 1u : (mode == 3 ? 2u : 3u))))) ? 1 : 0;
   __syncthreads();
   if (!s_go) return;
   const uint32_t ns = S.ns, prec = 1u << S.prec_bits, L = prec * 4;
@@ -602,7 +614,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_pgram(GeoDecJob *jobs, GeoJ
   const int d = blockIdx.z;
   if (J.status != 0 || G.status != 0 || d >= J.ndec) return;
   const GDAtt &A = J.att[d];
-  if (!(A.pred_method == 1 || A.pred_method == 0)) return;
+  if (!(A.pred_method == 1 || A.pred_method == 0) || A.table > 2) return;      // (table 3: k_m3_pgram)
   const int t = A.table, p = (int)(blockIdx.x * UVOL_BLOCK + threadIdx.x);
   if (p >= (int)G.ne[t]) return;
   int32_t *nb = J.nbr + (size_t)d * ((size_t)3 * J.ecap + 64) + 3 * (size_t)p;
@@ -777,7 +789,7 @@ __global__ void __launch_bounds__(64) k_gdec_pred(GeoDecJob *jobs, GeoJob *gj, i
   __syncthreads();
   if (!s_go) return;
   GDAtt &A = J.att[d];
-  if (A.pred_method == 6) return;                       // normals: k_gdec_flips + k_gdec_normals
+  if (A.pred_method == 6 || A.table > 2) return;        // normals: k_gdec_flips + k_gdec_normals; table 3: k_m3_pred
   const bool needs_pos = A.pred_method == 5;
   if ((phase == 0) == needs_pos) return;
   const int t = A.table, nc = A.nc, ne = (int)G.ne[t];
@@ -950,7 +962,7 @@ __global__ void __launch_bounds__(64) k_gdec_counts_early(GeoDecJob *jobs, int p
   if (J.method == 0) { if (phase == 0) { for (int d = 0; d < J.ndec; d++) J.rs[6 + d].early = 1; J.rs[GD_NRS - 1].early = 1; } return; }
   for (int d = 0; d < J.ndec; d++) {
     const int t = J.att[d].table;
-    if ((t == 0) != (phase == 0)) continue;
+    if ((t == 0) != (phase == 0) || t > 2) continue;      // (table 3: counted by its own traversal, if the call runs one)
     const uint32_t ne = t == 0 ? (uint32_t)J.nev : (t - 1 < J.nad ? (uint32_t)J.t_nv[t - 1] : 0u);
     GDRans &S = J.rs[6 + d];
     if (ne != 0 && ne <= J.ecap) { S.nvals = ne * (uint32_t)J.att[d].nc; S.early = 1u + (uint32_t)phase; }
@@ -964,6 +976,7 @@ __global__ void __launch_bounds__(64) k_gdec_counts(GeoDecJob *jobs, GeoJob *gj)
   if (J.method == 0) { G.ne[0] = (uint32_t)J.nv; for (int d = 0; d < J.ndec; d++) J.rs[6 + d].redo = J.rs[6 + d].early ? 0u : 1u; J.rs[GD_NRS - 1].redo = J.rs[GD_NRS - 1].early ? 0u : 1u; return; }      // sequential: one entry per point, the value counts were known at once
   for (int d = 0; d < J.ndec; d++) {
     GDRans &S = J.rs[6 + d];
+    if (J.att[d].table > 2) { S.redo = 0; S.nvals = 0; continue; }      // (the values of a decoder on table 3 are skipped here)
     const uint32_t nv = G.ne[J.att[d].table] * (uint32_t)J.att[d].nc;
     S.redo = (S.early && S.nvals == nv) ? 0u : 1u;
     S.nvals = nv;
@@ -1010,15 +1023,23 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_finish(GeoDecJob *jobs, Geo
 }
 
 // Material ids (thread per face): the value of the entry of the face's first corner, for the first decoder that holds a GENERIC (4) UINT8 (2)
-// one-component attribute on the base table (a vertex attribute, dec_type 0) of an edgebreaker file - what stock draco_encoder writes for
-// `usemtl` lines while no two materials meet at a vertex.  A generic attribute of another shape decodes as before and reports no material.
+// one-component attribute with plain integer values of an edgebreaker file, either on the base table (a vertex attribute, dec_type 0 - what
+// stock draco_encoder writes for `usemtl` lines while no two materials meet at a vertex) or on the seam-cut table of its own attribute-data
+// slot (a corner attribute, dec_type 1 - what uvol_params.material_seams writes where they do).  The value at corner c is
+// vals[v2d[table][corner-to-vertex map of that table][c]]; the third table's maps are the material pass's own (geo_mattab_dec.hpp), which only
+// the calls that return materials run.  A generic attribute of another shape decodes as before and reports no material.
 // gd_mat_decoder / gd_mat_value are the one statement of that rule: k_gdec_facemat and the packed weld (geo_weld.hpp) both go through them.
 __device__ __forceinline__ int gd_mat_decoder(const GeoDecJob &J) {
   if (J.method != 1) return -1;
-  for (int k = 0; k < J.ndec; k++) { const GDAtt &A = J.att[k]; if (A.att_type == 4 && A.data_type == 2 && A.ncomp == 1 && A.dec_type == 0 && A.table == 0 && A.seq_type == 1) return k; }
+  for (int k = 0; k < J.ndec; k++) { const GDAtt &A = J.att[k]; if (A.att_type != 4 || A.data_type != 2 || A.ncomp != 1 || A.seq_type != 1) continue;
+    if (A.dec_type == 0 ? A.table == 0 : (A.table == 1 || A.table == 2 || (A.table == 3 && J.m3.on && J.m3.dec == k))) return k; }
   return -1;
 }
-__device__ __forceinline__ uint8_t gd_mat_value(const GeoDecJob &J, const GeoJob &G, int d, size_t corner) { return (uint8_t)J.att[d].vals[G.v2d[0][J.c2v[corner]]]; }
+__device__ __forceinline__ uint8_t gd_mat_value(const GeoDecJob &J, const GeoJob &G, int d, size_t corner) {
+  const int t = J.att[d].table;
+  const int32_t e = t == 0 ? G.v2d[0][J.c2v[corner]] : (t == 3 ? J.m3.v2d[J.t_c2v[2][corner]] : G.v2d[t][J.t_c2v[t - 1][corner]]);
+  return (uint32_t)e < J.ecap ? (uint8_t)J.att[d].vals[e] : (uint8_t)0;      // (an entry past the workspace: a vertex no traversal reached, corrupt tables)
+}
 __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_facemat(GeoDecJob *jobs, GeoJob *gj) {
   GeoDecJob &J = jobs[blockIdx.y]; const GeoJob &G = gj[blockIdx.y];
   if (J.status != 0) return;
@@ -1030,6 +1051,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_facemat(GeoDecJob *jobs, Ge
   J.o_mat[f] = gd_mat_value(J, G, d, 3 * (size_t)f);
 }
 
+#include "geo_mattab_dec.hpp"
 #define GEO_SCAN_BLOCK_ONLY
 #include "geo_scan.hpp"
 #include "geo_weld.hpp"
@@ -1066,6 +1088,37 @@ extern "C" int uvol_drc_info(const uint8_t *drc, size_t len, uint32_t *n_faces, 
   return UVOL_OK;
 }
 
+// Does the file carry its material as a corner attribute?  A look at the decoder rows of the file in HOST memory, where the call's inputs lie
+// (k_gdec_index's walk up to the rows; nothing is read back from the device): bit 0 = a corner attribute on attribute-data slot 2 - the frame
+// needs the third table's pass (geo_mattab_dec.hpp) -, bit 1 = a GENERIC uint8 one-component corner attribute in any slot - the packed weld
+// needs the value at every corner.  A file the walk cannot follow gives 0: the device reports it.  A call none of whose frames has the bit
+// neither enqueues nor carves the pass.
+static int gdec_corner_material(const uint8_t *b, size_t n) {
+  if (!b || n < 16 || n > 0xffffffffu || b[8] != 1) return 0;
+  GRd r; r.b = b; r.n = (uint32_t)n; r.o = 11; r.err = 0;
+  const int trav = (int)gr_u8(r);
+  (void)gr_varint(r); const uint32_t nf = gr_varint(r); const int nad = (int)gr_u8(r); (void)gr_varint(r); (void)gr_varint(r); const uint32_t nts = gr_varint(r);
+  if (r.err || nad < 1 || nad > GD_MAXAD || nts > nf || (trav != 0 && trav != 2)) return 0;
+  for (uint32_t i = 0; i < 2 * nts && !r.err; i++) (void)gr_varint(r);
+  if (nts > 0) { if (r.err || (nts + 7) / 8 > r.n - r.o) return 0; r.o += (nts + 7) / 8; }
+  if (trav == 0) { const uint32_t nb = gr_varint(r); if (r.err || nb > r.n - r.o) return 0; r.o += nb; }
+  GDRabs B;
+  for (int i = 0; i < 1 + nad; i++) gr_rabs(r, B);
+  for (int i = 0; i < 6 && trav == 2 && !r.err; i++) { GDRans S{}; S.max_ns = GD_CTX_NS; S.max_prec_bits = 12; const uint32_t cn = gr_varint(r); if (cn > 0 && !r.err) gr_rans(r, S, cn); }
+  const int ndec = (int)gr_u8(r);
+  if (r.err || ndec < 1 || ndec > GD_MAXDEC) return 0;
+  int slot[GD_MAXDEC], dtype[GD_MAXDEC], flags = 0;
+  for (int d = 0; d < ndec; d++) { slot[d] = (int8_t)gr_u8(r); dtype[d] = (int)gr_u8(r); (void)gr_u8(r); }
+  for (int d = 0; d < ndec && !r.err; d++) {
+    if (gr_varint(r) != 1) return 0;
+    const int att_type = (int)gr_u8(r), data_type = (int)gr_u8(r), ncomp = (int)gr_u8(r); (void)gr_u8(r); (void)gr_varint(r); (void)gr_u8(r);
+    if (r.err || dtype[d] != 1 || slot[d] < 0 || slot[d] >= nad) continue;
+    if (slot[d] == 2) flags |= 1;
+    if (att_type == 4 && data_type == 2 && ncomp == 1) flags |= 2;
+  }
+  return r.err ? 0 : flags;
+}
+
 // geom_encode.hip: k_pack_faces + k_traverse + k_v2d over tables 1..3 of a GeoJob array (the encoder's own sequencing kernels)
 int geo_run_traversals(uvol_ctx *ctx, GeoJob *gj, int n, uint32_t max_nfi, uint32_t max_vals);
 bool geo_records8(uint32_t max_nfi);
@@ -1096,9 +1149,11 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_gdec_clear(GeoDecJob *jobs) {
 // so its arrays share the addresses of the predictors' and the frame's peak does not grow.  3 / 4: the same two for
 // uvol_decode_mesh_batch_packed - 16 bytes of staging per point, and the decoded integers (att[].vals) and the two maps the material fetch
 // reads (c2v, v2d[0]) stay alive up to the weld, which gathers them; the other entry points' placement does not change.
-enum { DS_INDEX = 0, DS_CTX, DS_CONN, DS_TABLES, DS_TRAV, DS_SYM, DS_PRED, DS_FIN, DS_WELD, DS_COUNT };
+// mat3: the third seam-cut table's pass (geo_mattab_dec.hpp; the calls that return materials): its arrays live in a stage of their own, DS_MAT,
+// between the predictors and the outputs, and share the predictors' addresses; only its inverse map lives on to the outputs.
+enum { DS_INDEX = 0, DS_CTX, DS_CONN, DS_TABLES, DS_TRAV, DS_SYM, DS_PRED, DS_MAT, DS_FIN, DS_WELD, DS_COUNT };
 struct GDWeldStage { uint32_t *index; uint8_t *vals; };
-static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool full, GDPlan &P, int weld = 0, GDWeldStage *stage = nullptr) {
+static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool full, GDPlan &P, int weld = 0, GDWeldStage *stage = nullptr, bool mat3 = false) {
   const size_t nf = (size_t)J.nf, nc = 3 * nf, maxv = (size_t)J.nev + nf + 8;          // nsplit <= nf
   const size_t E = full ? nc + 3 : std::min(nc + 3, nf + nf / 2 + 4096);
   const bool packed = weld >= 3; const int DS_VALS = packed ? DS_WELD : DS_FIN;
@@ -1128,9 +1183,18 @@ static size_t gdec_carve(GeoDecJob &J, GeoJob &G, uint8_t *base, bool r8, bool f
     DCARVE(J.w.cnt, 4 * (E + 2), DS_WELD, DS_WELD); DCARVE(J.w.fan, 4 * nc, DS_WELD, DS_WELD); DCARVE(J.w.rep, 4 * nc, DS_WELD, DS_WELD); DCARVE(J.w.pid, 4 * nc, DS_WELD, DS_WELD);
     DCARVE(J.w.bsum_p, 4 * (E / UVOL_BLOCK + 4), DS_WELD, DS_WELD); DCARVE(J.w.bsum_c, 4 * (nc / UVOL_BLOCK + 4), DS_WELD, DS_WELD);
     if (weld == 2 || weld == 4) { DCARVE(stg.index, 4 * nc, DS_WELD, DS_WELD); DCARVE(stg.vals, (packed ? 16 : 32) * nc, DS_WELD, DS_WELD); }      // (n_points <= corners)
+    if (packed) DCARVE(J.w.cmat, nc + 16, DS_FIN, DS_WELD);
+  }
+  J.m3 = GDMatTab{}; J.m3.dec = -1;
+  if (mat3) {
+    J.m3.on = 1;
+    DCARVE(J.m3.vopen, E + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); DCARVE(J.m3.fvis, nf / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED); DCARVE(J.m3.vvis, E / 8 + 64, UVOL_WS_PINNED, UVOL_WS_PINNED);
+    DCARVE(J.m3.ropp, 4 * nc, DS_MAT, DS_MAT); DCARVE(J.m3.order, 4 * (E + 3), DS_MAT, DS_MAT); DCARVE(J.m3.v2d, 4 * (E + 3), DS_MAT, DS_FIN); DCARVE(J.m3.stack, 4 * (nf + 2), DS_MAT, DS_MAT);
+    DCARVE(J.m3.nbr, 4 * (3 * E + 64), DS_MAT, DS_MAT); DCARVE(J.m3.syms, 4 * (E + 4), DS_MAT, DS_MAT);
+    DCARVE(J.m3.probs, 4 * (size_t)M3_NS, DS_MAT, DS_MAT); DCARVE(J.m3.cum, 4 * (size_t)M3_NS, DS_MAT, DS_MAT); DCARVE(J.m3.lut, 4 * (size_t)(1u << M3_PREC_BITS), DS_MAT, DS_MAT);
   }
 #undef DCARVE
-  const std::vector<uint64_t> key = { (uint64_t)nf, (uint64_t)J.nev, (uint64_t)r8 | ((uint64_t)full << 1) | ((uint64_t)weld << 2), (uint64_t)items.size() };
+  const std::vector<uint64_t> key = { (uint64_t)nf, (uint64_t)J.nev, (uint64_t)r8 | ((uint64_t)full << 1) | ((uint64_t)weld << 2) | ((uint64_t)mat3 << 5), (uint64_t)items.size() };
   if (key != P.key) { P.total = uvol_ws_place(items, &P.zero, DS_COUNT, "geometry decode"); P.offs.resize(items.size()); for (size_t i = 0; i < items.size(); i++) P.offs[i] = items[i].off; P.key = key; }
   for (size_t i = 0; i < slots.size(); i++) *slots[i] = base ? (void *)(base + P.offs[i]) : nullptr;
   if (stage) *stage = stg;
@@ -1174,6 +1238,11 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
                                  uint8_t *const *fmat, int *has_mat, uvol_decoded_points *pts, uvol_packed_points *pk) {
   const bool want_mat = fmat != nullptr || has_mat != nullptr;
   const int weld = pts ? (out_dev ? 1 : 2) : pk ? (out_dev ? 3 : 4) : 0;
+  // the calls that return materials: the third seam-cut table's pass (geo_mattab_dec.hpp) where a frame of the call carries such a material;
+  // the packed form further takes the value at every corner of a frame whose material is a corner attribute in any slot (the weld's fourth key)
+  int corner_mat = 0;
+  if (want_mat || pk) for (int i = 0; i < n; i++) corner_mat |= gdec_corner_material(files[i], lens[i]);
+  const bool mat3 = (corner_mat & 1) != 0, corner_keys = pk != nullptr && (corner_mat & 2) != 0;
   GeoDecState *T = ctx->geodec;
   if (n <= 0) return UVOL_OK;
   T->hjobs.assign((size_t)n, GeoDecJob{}); T->hg.assign((size_t)n, GeoJob{});
@@ -1189,7 +1258,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GeoDecJob &J = T->hjobs[i]; J.nf = (int32_t)nf; J.nev = (int32_t)nev; J.file_len = (uint32_t)lens[i];
     max_nf = std::max(max_nf, nf); max_nev = std::max(max_nev, nev);
     foff[i] = ftot; ftot += a256(lens[i] + 16);
-    GeoJob gtmp{}; const size_t w = gdec_carve(J, gtmp, nullptr, r8, full, T->plan, weld);
+    GeoJob gtmp{}; const size_t w = gdec_carve(J, gtmp, nullptr, r8, full, T->plan, weld, nullptr, mat3);
     woff[i] = wtot; wtot += a256(w);
     { const size_t nc = 3 * (size_t)nf; ooff[i] = otot; otot += 3 * ((pk ? 0 : a256(4 * 3 * nc)) + a256(4 * nc)) + (want_mat ? a256(nf) : 0); }      // (packed: the index streams alone)
   }
@@ -1206,7 +1275,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     ups.push_back(UvolUpItem{ foff[i], files[i], lens[i] });      // one staged upload for the whole call below (1920 pageable copies cost ~0.1 s)
     J.file = fd; J.status = 0;
     GDWeldStage stg{ nullptr, nullptr };
-    (void)gdec_carve(J, G, (uint8_t *)T->slab.p + woff[i], r8, full, T->plan, weld, &stg);
+    (void)gdec_carve(J, G, (uint8_t *)T->slab.p + woff[i], r8, full, T->plan, weld, &stg, mat3);
     const size_t nc = 3 * (size_t)J.nf;
     if (pts) {                                                               // device outputs are written where the caller wants them; host outputs are staged in the workspace
       const uvol_decoded_points &P = pts[i]; GDWeldJob &W = J.w;
@@ -1218,7 +1287,7 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     }
     if (pk) {
       const uvol_packed_points &P = pk[i]; GDWeldJob &W = J.w;
-      W.on = 1; W.packed = 1; W.mat_dec = -1; W.layout = UVOL_POINTS_INTERLEAVED; W.cap = (uint32_t)std::min(P.cap_points, nc); W.np = 0;
+      W.on = 1; W.packed = 1; W.mat_dec = -1; W.mat_corner = 0; W.layout = UVOL_POINTS_INTERLEAVED; W.cap = (uint32_t)std::min(P.cap_points, nc); W.np = 0;
       W.o_index = !P.index ? nullptr : (out_dev ? P.index : stg.index);
       W.o_val[0] = !P.records ? nullptr : (out_dev ? (float *)P.records : (float *)stg.vals); W.o_val[1] = W.o_val[2] = nullptr;
     }
@@ -1276,6 +1345,17 @@ static int geo_decode_batch_impl(uvol_ctx *ctx, const uint8_t *const *files, con
     GLAUNCH(k_gdec_normals, dim3(bc, N, GD_MAXDEC), dim3(UVOL_BLOCK), 0, dj, gj);
     GLAUNCH(k_gdec_uvgeo, dim3(bc, N, GD_MAXDEC), dim3(UVOL_BLOCK), 0, dj, gj);
     GLAUNCH(k_gdec_pred, dim3(N, GD_MAXDEC), dim3(64), 0, dj, gj, 1); }
+  if (mat3 || corner_keys) { uvol_ctx::Scope sc(ctx, "geodec.k7b_material_table", 0);
+    const unsigned bm = std::min<unsigned>(bc, M3_GRID);
+    if (mat3) {
+    GLAUNCH(k_m3_setup, dim3(N), dim3(64), 0, dj);
+    GLAUNCH(k_m3_open, dim3(bm, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_m3_traverse, dim3(N), dim3(64), 0, dj);
+    GLAUNCH(k_m3_v2d, dim3(bm, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_gdec_rans, dim3(N, GD_MAXDEC), dim3(64), 0, dj, 6, GD_MAXDEC, 4);
+    GLAUNCH(k_m3_pgram, dim3(bm, N), dim3(UVOL_BLOCK), 0, dj);
+    GLAUNCH(k_m3_pred, dim3(N), dim3(64), 0, dj); }
+    if (corner_keys) GLAUNCH(k_m3_cornermat, dim3(bm, N), dim3(UVOL_BLOCK), 0, dj, gj); }      // (the weld's fourth key, while the tables' maps are alive)
   if (pk) { uvol_ctx::Scope sc(ctx, "geodec.k8_keys_packed", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj); }      // o_val is null: the index streams (the weld's keys) and nothing else
   else { uvol_ctx::Scope sc(ctx, "geodec.k8_finish", 0); GLAUNCH(k_gdec_finish, dim3(bc, N, 3), dim3(UVOL_BLOCK), 0, dj, gj);
     if (want_mat) GLAUNCH(k_gdec_facemat, dim3(uvol_blocks(max_nf), N), dim3(UVOL_BLOCK), 0, dj, gj); }

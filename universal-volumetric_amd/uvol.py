@@ -652,7 +652,7 @@ class Codec:
     def decode_mesh_batch(self, files, raise_on_error=True, fetch=True, views=False, arena=None, materials=False):
         """files: list of .drc bytes -> list of dicts {pos [n,3], uv [n,2], nrm [n,3] float32 in decoding order,
         idx_pos / idx_uv / idx_nrm [3*faces] uint32 entry index per corner, face_mat [faces] uint8 material id per face}; absent attributes
-        (and face_mat of a file without a GENERIC uint8 one-component vertex attribute) are None.  face_mat is only there with materials=True
+        (and face_mat of a file without a GENERIC uint8 one-component vertex or corner attribute) are None.  face_mat is only there with materials=True
         (uvol_decode_mesh_batch_mat: one more kernel and one more array per frame; size an arena with decode_arena_bytes(files, materials=True)).
         arena (a PinnedArena, with views=True): the output arrays are carved from it - outputs that all lie in uvol_host_alloc memory are written
         by the DMA engines where they are, without the library's staging buffers."""
@@ -779,7 +779,8 @@ class Codec:
         (uint16 pos[3], uint16 material, uint16 uv[2], int8 nrm[4]: the file's quantised integers, the normal times 127 rounded), index
         [3*faces] uint32 point per corner, n_faces, n_points, has_uv, has_nrm, has_material, pos_bits, uv_bits, pos_min [3], pos_scale, uv_min
         [2], uv_scale (float32: value = min + q * scale, product rounded before the sum)}.  Points and index are those of
-        decode_mesh_batch_points.  The other arguments are those of decode_mesh_batch_points, `metas` a (PackedPoints * n) array; a
+        decode_mesh_batch_points, except in a frame whose material is a corner attribute (interior material seams): there the corner's material
+        is part of the point tuple, and a point shared by two materials becomes one point per material.  The other arguments are those of decode_mesh_batch_points, `metas` a (PackedPoints * n) array; a
         PinnedArena of points_arena_bytes(files) is large enough."""
         files = [bytes(f) for f in files]; n = len(files)
         fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
