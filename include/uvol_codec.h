@@ -171,6 +171,36 @@ int uvol_inflate_png_batch_dev(uvol_ctx *ctx, const uint8_t *const *zlib_streams
  * status[i] = UVOL_OK or UVOL_E_INVALID, n <= the images of that call.  status == NULL: the first failure is the return value. */
 int uvol_png_status(uvol_ctx *ctx, int slot, int *status, int n);
 
+/* ---- reduced-resolution texture layers (additive: uvol_abi_version stays 1) ----
+ * The player manifest gives every texture target its own `resolution` (reference src/Interfaces.ts:41-73, :113-131), so that one capture is
+ * served in several sizes; the raw `etc2` target in particular exists for the devices that cannot afford the transcoder
+ * (src/V2/player.ts:207-222) - nor 2048^2 per frame.  This entry point makes the smaller layers on the device, from the full-size layers
+ * that lie in HBM after uvol_unfilter_png_batch_dev / uvol_inflate_png_batch_dev anyway: n RGBA8 layers of width x height (rgba[i]: width *
+ * height * 4 bytes, top row first) are downscaled by factor = 2, 4 or 8 in ONE kernel launch; rgba_dev_out[i] is a DEVICE pointer to
+ * ceil(width / factor) x ceil(height / factor) x 4 bytes in the context's downscale slot `slot` (0 / 1), valid until that slot is written
+ * again, and is what uvol_encode_texture_segment[s]_dev[_async] takes.
+ * inputs_on_device: rgba[i] are device pointers (4-byte aligned; layers of a PNG ingest slot are ordered behind their un-filter, as the
+ * texture entry points do it); otherwise host memory, uploaded through the library's staging buffers.
+ * The filter is this project's own, defined exactly in integers (stock `basisu -mipmap` uses a Kaiser window in linear light, which nothing
+ * at hand pins): output texel (X, Y) is made in ONE step - never by repeated halving - from the box B of the n input texels with
+ * factor X <= x < min(factor X + factor, width), factor Y <= y < min(factor Y + factor, height).
+ *   lin[v] = floor(65535 L(v / 255) + 0.5), v = 0 .. 255, L = the sRGB decoding function (s / 12.92 for s <= 0.04045, else
+ *            ((s + 0.055) / 1.055)^2.4), in double; strictly increasing, lin[1] = 20, lin[254] = 64952, lin[255] = 65535.
+ *   alpha:   A = sum of a over B; out.a = (2 A + n) / (2 n), integer division.
+ *   colour:  alpha-weighted in linear light, so that a transparent neighbour does not bleed into an opaque texel.  Per channel c of r, g, b:
+ *            N = sum lin[c] a, D = A - or, when A == 0, N = sum lin[c], D = n -; m = (2 N + D) / (2 D), integer division; out.c = the v
+ *            with the smallest |lin[v] - m|, the lower v at a tie.
+ * A constant image maps to itself; a 2 x 2 black / white opaque checker gives (188, 188, 188, 255), where a byte average would give 128.
+ * Blocking: like the other blocking entry points it first waits for the context's enqueued calls - so a slot an enqueued encode still reads
+ * is never overwritten - and returns when the layers are complete.  There is NO host-output form (the layers exist to be encoded from HBM)
+ * and NO enqueue form (the kernel moves 17 MB per 2048^2 layer once; the encode that follows is what takes time).  uvol_trim gives the slots
+ * back, uvol_ctx_destroy frees them.  Mip levels inside one .ktx2 stay out of scope; the kernel is what they would use.
+ * UVOL_E_INVALID with a message, before anything runs: a factor other than 2 / 4 / 8, a slot other than 0 / 1, a NULL layer (or a device
+ * layer that is not 4-byte aligned), width or height zero or beyond the limits of uvol_unfilter_png_batch_dev (8192 x 16384).  n <= 0 is
+ * UVOL_OK and does nothing. */
+int uvol_downscale_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height,
+                                  int inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
+
 /* GPU-resident form (SURVEY 8(b) "variants taking arrays of frames + hipStream_t"; caller-owned buffers as in
  * deprecated/encoder_legacy/codec/corto_codec.h:41-43): inputs are device pointers PRODUCED ON `producer_stream` (a hipStream_t passed
  * as void *, NULL = already complete) - the codec's kernels are ordered after the work queued on that stream so far, without a host

@@ -269,7 +269,7 @@ void uvol_ctx_destroy(uvol_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   ctx->resolve_profile();
   geo_destroy(ctx); tex_destroy(ctx); uvol_uplink_destroy(ctx);      // (the lanes' streams are synchronised and gone before the slots they read are freed)
-  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx);
+  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx); down_destroy(ctx);
   for (int k = 0; k < 2; k++) { if (ctx->up_pin[k]) (void)hipHostFree(ctx->up_pin[k]); if (ctx->up_ev[k]) (void)hipEventDestroy(ctx->up_ev[k]); }
   for (int k = 0; k < 2; k++) if (ctx->pin_ev[k]) (void)hipEventDestroy(ctx->pin_ev[k]);
   for (int k = 0; k < 2; k++) { if (ctx->dn_pin[k]) (void)hipHostFree(ctx->dn_pin[k]); if (ctx->dn_ev[k]) (void)hipEventDestroy(ctx->dn_ev[k]); }
@@ -301,6 +301,7 @@ int uvol_trim(uvol_ctx *ctx) {
   int rt = geo_trim(ctx);
   const int ru = tex_trim(ctx); if (rt == UVOL_OK) rt = ru;
   uvol_uplink_trim(ctx);
+  down_trim(ctx);
   return rc != UVOL_OK ? rc : (rf != UVOL_OK ? rf : (rx != UVOL_OK ? rx : rt));
 }
 
@@ -677,6 +678,14 @@ int uvol_inflate_png_batch_dev(uvol_ctx *ctx, const uint8_t *const *zlib_streams
   if (!ctx || !zlib_streams || !lens || n < 0 || !rgba_dev_out) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
   return png_ingest_batch(ctx, zlib_streams, lens, n, width, height, channels, slot, rgba_dev_out);
+}
+int uvol_downscale_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height, int inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx) return UVOL_E_INVALID;
+  if (n <= 0) return UVOL_OK;
+  if (!rgba || !rgba_dev_out) { ctx->set_error("uvol_downscale_rgba_batch_dev: %s is NULL", !rgba ? "rgba" : "rgba_dev_out"); return UVOL_E_INVALID; }
+  (void)hipSetDevice(ctx->device);
+  return down_rgba_batch(ctx, rgba, n, width, height, inputs_on_device != 0, factor, slot, rgba_dev_out);
 }
 int uvol_png_status(uvol_ctx *ctx, int slot, int *status, int n) {
   if (!ctx) return UVOL_E_INVALID;

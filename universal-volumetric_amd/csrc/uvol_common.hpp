@@ -157,6 +157,7 @@ struct GeoDecState;  // geometry decode state (geom_decode.hip)
 struct UastcState;   // UASTC texture mode (tex_uastc.hip)
 struct ObjState;     // OBJ text ingest on the device (obj_ingest.hip)
 struct PngState;     // PNG scanlines un-filtered on the device (png_ingest.hip)
+struct DownState;    // RGBA layers downscaled on the device (tex_downscale.hip)
 
 struct uvol_ctx {
   int device = 0;
@@ -174,6 +175,7 @@ struct uvol_ctx {
   UastcState *uastc = nullptr;
   ObjState *obj = nullptr;
   PngState *png = nullptr;
+  DownState *down = nullptr;      // created by the first uvol_downscale_rgba_batch_dev
   // enqueue form of the ABI (uvol_*_async + uvol_sync): calls run in order on this context's worker thread
   struct AsyncQ {
     std::mutex m; std::condition_variable cv_work, cv_idle; std::deque<std::function<int()>> q; std::thread th; bool busy = false, stop = false; int first_err = 0; char err[512] = {0};
@@ -265,6 +267,10 @@ int png_wait(uvol_ctx *ctx);
 int png_unfilter_batch(uvol_ctx *ctx, const uint8_t *const *raw, int n, uint32_t w, uint32_t h, int channels, int slot, const uint8_t **rgba_dev_out);
 int png_ingest_batch(uvol_ctx *ctx, const uint8_t *const *raw, const size_t *zlens, int n, uint32_t w, uint32_t h, int channels, int slot, const uint8_t **rgba_dev_out);
 int png_status(uvol_ctx *ctx, int slot, int *status, int n);
+// uvol_downscale_rgba_batch_dev (tex_downscale.hip); the state is created by the first call
+int down_rgba_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
+void down_trim(uvol_ctx *ctx);
+void down_destroy(uvol_ctx *ctx);
 int uastc_create(uvol_ctx *ctx);
 void uastc_destroy(uvol_ctx *ctx);
 #define UASTC_PROBE_SUPERCOMPRESSED (-10)      /* a UASTC .ktx2 (DFD colour model 166) whose level data are Zstandard-supercompressed */

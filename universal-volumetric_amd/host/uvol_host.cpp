@@ -517,7 +517,7 @@ bool audio_duration(const std::string &path, double &seconds, std::string &err) 
 }
 
 // ------------------------------------------------------------------ manifests
-Json manifest_player(const Config &c, long geo_frames, long tex_segments, uint32_t tw, uint32_t th, int pad, long etc2_frames) {
+Json manifest_player(const Config &c, long geo_frames, long tex_segments, uint32_t tw, uint32_t th, int pad, long etc2_frames, const std::vector<TexRung> &rungs, uint32_t etc2_w, uint32_t etc2_h) {
   const std::string hashes = "[" + std::string((size_t)pad, '#') + "]";
   Json m = Json::object();
   m.set("version", Json::string("v2"));
@@ -532,10 +532,17 @@ Json manifest_player(const Config &c, long geo_frames, long tex_segments, uint32
   tt.set("ktx2", td);
   if (etc2_frames > 0) {                    // raw ETC2 RGB (ETC1 subset) blocks, one frame per file: sequenceSize 1 (the player indexes segments, src/V2/player.ts:418-446)
     Json te = Json::object(), res2 = Json::array();
-    res2.arr.push_back(Json::number(tw, true)); res2.arr.push_back(Json::number(th, true));
+    res2.arr.push_back(Json::number(etc2_w ? etc2_w : tw, true)); res2.arr.push_back(Json::number(etc2_h ? etc2_h : th, true));      // (--etc2-scale: a rung's size)
     te.set("format", Json::string("etc2")); te.set("resolution", res2); te.set("type", Json::string("baseColor")); te.set("tag", Json::string("default"));
     te.set("sequenceSize", Json::number(1, true)); te.set("sequenceCount", Json::number((double)etc2_frames, true)); te.set("frameRate", Json::number(c.texture_frame_rate));
     tt.set("etc2", te);
+  }
+  for (const TexRung &r : rungs) {           // reduced-resolution tiers (--texture-ladder): behind the targets the stock player knows
+    Json tr = Json::object(), rr = Json::array();
+    rr.arr.push_back(Json::number(r.w, true)); rr.arr.push_back(Json::number(r.h, true));
+    tr.set("format", Json::string("ktx2")); tr.set("resolution", rr); tr.set("type", Json::string("baseColor")); tr.set("tag", Json::string("default"));
+    tr.set("sequenceSize", Json::number(c.ktx2_batch_size, true)); tr.set("sequenceCount", Json::number((double)tex_segments, true)); tr.set("frameRate", Json::number(c.texture_frame_rate));
+    tt.set("ktx2_" + std::to_string(r.w) + "x" + std::to_string(r.h), tr);
   }
   t.set("targets", tt); t.set("path", Json::string("texture_[target]_[type]_[tag]/" + hashes + "[ext]")); m.set("texture", t);
   return m;

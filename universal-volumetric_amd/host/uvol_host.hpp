@@ -92,7 +92,13 @@ bool audio_duration(const std::string &path, double &seconds, std::string &err);
 // The shape src/V2/player.ts reads (src/Interfaces.ts:75-132): targets are objects keyed by target name.
 // extra_etc2_frames > 0 adds the raw `etc2` texture target next to `ktx2` (src/Interfaces.ts:19, :60-73; src/V2/player.ts:208-222 picks
 // the supported target of highest TEXTURE_FORMAT_PRIORITY, :338-356 loads one raw ETC2 RGB image per .etc2 file): one file per frame
-Json manifest_player(const Config &c, long geometry_frames, long texture_segments, uint32_t tex_w, uint32_t tex_h, int pad_width, long extra_etc2_frames = 0);
+// rungs: the reduced-resolution tiers of `uvolenc --texture-ladder` (src/Interfaces.ts:41-73: every texture target carries its own
+// `resolution`): one target `ktx2_<w>x<h>` per rung, format `ktx2`, with the segment counts and frame rate of `ktx2`, listed AFTER `ktx2` and
+// `etc2` - the stock player's selection skips names it does not know (src/utils.ts:26-32), so its choice is unchanged; a host application
+// picks a tier by name.  etc2_w / etc2_h != 0: the resolution of the `etc2` target (`--etc2-scale`: transcoded from a rung's segments).
+struct TexRung { uint32_t w, h; };
+Json manifest_player(const Config &c, long geometry_frames, long texture_segments, uint32_t tex_w, uint32_t tex_h, int pad_width, long extra_etc2_frames = 0,
+                     const std::vector<TexRung> &rungs = {}, uint32_t etc2_w = 0, uint32_t etc2_h = 0);
 // The literal dict scripts/Encoder.py:311-328 writes (kept behind --encoder-py-manifest).
 Json manifest_encoder_py(const Config &c, long geometry_frames, long texture_segments, const std::string &drc_rel, const std::string &ktx2_rel);
 

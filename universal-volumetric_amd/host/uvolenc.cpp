@@ -4,9 +4,15 @@
 // player reads (src/Interfaces.ts:75-132, src/V2/player.ts:141-174).
 //
 //   uvolenc project-config.json [--gpus N] [--device D] [--batch-frames F] [--ingest-threads T] [--targets ktx2[,etc2]] [--uastc] [--material-seams] [--device-inflate [--tex-batch-frames F]]
-//                               [--force] [--encoder-py-manifest]
+//                               [--texture-ladder F[,F...] [--etc2-scale F]] [--force] [--encoder-py-manifest]
 //   --targets   texture targets to write (src/Interfaces.ts:19 TextureFileFormat): `ktx2` always; `etc2` adds one raw ETC2 RGB
 //               (ETC1-subset) block image per frame, transcoded on the GPU from the ETC1S segments, and a second target in the manifest
+//   --texture-ladder   reduced-resolution tiers (src/Interfaces.ts:41-73: every texture target has its own `resolution`): for every factor F of
+//               2, 4, 8 the layers of a texture batch are downscaled on the GPU (uvol_downscale_rgba_batch_dev) after its full-size segments are
+//               encoded, encoded through the same entry points and written to texture_ktx2_<w>x<h>_baseColor_default/; the manifest lists a target
+//               `ktx2_<w>x<h>` per rung behind `ktx2` and `etc2` (the stock player's choice is unchanged; a host application picks a tier by name)
+//   --etc2-scale F   1 (default) or a factor of the ladder: the raw `etc2` target is transcoded from THAT rung's segments and carries its resolution
+//               (the tier the stock player picks on devices with the ETC extension, which cannot afford full-size frames either)
 //   --uastc     the KTX2 files carry UASTC LDR 4x4 blocks (`basisu -uastc`) instead of ETC1S/BasisLZ
 //   --material-seams   (or UVOL_MATERIAL_SEAMS=1) frames whose `usemtl` materials meet at shared vertices are written with the material
 //               attribute as a corner attribute instead of without it
@@ -61,6 +67,7 @@ int main(int argc, char **argv) {
   const auto t_start = std::chrono::steady_clock::now();
   { const char *e = std::getenv("UVOL_TIMING"); g_timing = e && *e == '1'; }
   int n_gpus = 1, device0 = 0, frames_per_batch = 32, ingest_threads = 0; bool force = false, encpy = false, want_etc2 = false, uastc = false, host_obj = false, host_png = false, dev_inflate = false, pinned_text = false, material_seams = false; int tex_batch_frames = 0;
+  std::vector<int> ladder; int etc2_scale = 1;      // --texture-ladder: the rungs' factors in the order given; --etc2-scale
   { const char *e = std::getenv("UVOL_MATERIAL_SEAMS"); material_seams = e && *e == '1'; }      // (= --material-seams)
   for (int i = 2; i < argc; i++) {
     if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) n_gpus = std::atoi(argv[++i]);
@@ -76,6 +83,17 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--uastc")) uastc = true;
     else if (!std::strcmp(argv[i], "--material-seams")) material_seams = true;      // frames whose materials meet at shared vertices keep their material attribute (uvol_params.material_seams)
     else if (!std::strcmp(argv[i], "--encoder-py-manifest")) encpy = true;
+    else if (!std::strcmp(argv[i], "--etc2-scale") && i + 1 < argc) etc2_scale = std::atoi(argv[++i]);
+    else if (!std::strcmp(argv[i], "--texture-ladder") && i + 1 < argc) {
+      const std::string t = argv[++i]; size_t a = 0;
+      while (a <= t.size()) {
+        size_t b = t.find(',', a); if (b == std::string::npos) b = t.size();
+        const std::string k = t.substr(a, b - a);
+        if (k != "2" && k != "4" && k != "8") { std::printf("❌ --texture-ladder takes factors 2, 4, 8 (got '%s')\n", k.c_str()); return 1; }
+        if (std::find(ladder.begin(), ladder.end(), std::atoi(k.c_str())) == ladder.end()) ladder.push_back(std::atoi(k.c_str()));
+        a = b + 1;
+      }
+    }
     else if (!std::strcmp(argv[i], "--targets") && i + 1 < argc) {
       const std::string t = argv[++i]; size_t a = 0;
       while (a <= t.size()) {
@@ -87,6 +105,7 @@ int main(int argc, char **argv) {
     }
   }
   if (want_etc2 && uastc) { std::printf("❌ the etc2 target is transcoded from ETC1S segments; it cannot be combined with --uastc\n"); return 1; }
+  if (etc2_scale != 1 && std::find(ladder.begin(), ladder.end(), etc2_scale) == ladder.end()) { std::printf("❌ --etc2-scale takes 1 or a factor of --texture-ladder (got %d)\n", etc2_scale); return 1; }
   std::vector<uint8_t> raw; if (!read_file(argv[1], raw)) { std::printf("❌ cannot read %s\n", argv[1]); return 1; }
   Config cfg; std::string err;
   if (!load_config(std::string(raw.begin(), raw.end()), cfg, err)) { std::printf("❌ %s\n", err.c_str()); return 1; }
@@ -126,6 +145,8 @@ int main(int argc, char **argv) {
   if (!cfg.obj_files_path.empty() && !make_dirs(geo_dir)) { std::printf("❌ cannot create %s\n", geo_dir.c_str()); return 1; }
   if (!cfg.images_path.empty() && (!make_dirs(tex_dir) || (want_etc2 && !make_dirs(etc_dir)))) { std::printf("❌ cannot create %s\n", tex_dir.c_str()); return 1; }
   if (want_etc2 && cfg.images_path.empty()) { std::printf("❌ --targets etc2 needs ImagesPath (the raw target is transcoded while the segments are encoded)\n"); return 1; }
+  if (!ladder.empty() && cfg.images_path.empty()) { std::printf("❌ --texture-ladder needs ImagesPath (the rungs are downscaled from the images while the segments are encoded)\n"); return 1; }
+  auto rung_dir = [&](uint32_t rw, uint32_t rh) { return join(cfg.output_directory, "texture_ktx2_" + std::to_string(rw) + "x" + std::to_string(rh) + "_baseColor_default"); };
   int pad = 5;
   std::atomic<int> geo_failed{-1};
   std::vector<std::thread> geo_threads;
@@ -392,35 +413,61 @@ int main(int argc, char **argv) {
           size_t q = 0; for (size_t s = 0; s < T->ns && bad_seg < 0; s++) for (size_t k = 0; k < T->imgs[s].size(); k++) if (pst[q++] != UVOL_OK) { bad_seg = (int)s; break; }
           if (bad_seg >= 0) { fail(starts[s0 + (size_t)bad_seg], "zlib inflate failed"); break; }
         }
+        // the segments of one size from their layers lp[s][k] (device or host memory): full segments in one batched call, segments with
+        // fewer layers one call each
+        auto encode_set = [&](const std::vector<std::vector<const uint8_t *>> &lp, bool dev, uint32_t ew, uint32_t eh, std::vector<std::unique_ptr<uint8_t[]>> &outs, std::vector<size_t> &lens) {
+          std::vector<size_t> full; for (size_t s = 0; s < T->ns; s++) if ((int)lp[s].size() == B) full.push_back(s);
+          if (!full.empty()) {
+            std::vector<const uint8_t *> ptrs; std::vector<uint8_t *> op; std::vector<size_t> caps, ln(full.size(), 0);
+            for (size_t s : full) { for (size_t k = 0; k < lp[s].size(); k++) ptrs.push_back(lp[s][k]); const size_t cap = uvol_texture_bound(ew, eh, B); outs[s].reset(new uint8_t[cap]); op.push_back(outs[s].get()); caps.push_back(cap); }
+            if ((dev ? uvol_encode_texture_segments_dev : uvol_encode_texture_segments)(tctxs[g], ptrs.data(), (int)full.size(), B, ew, eh, op.data(), caps.data(), ln.data()) != UVOL_OK) { fail(starts[s0 + full[0]], uvol_last_error(tctxs[g])); return; }
+            for (size_t q = 0; q < full.size(); q++) lens[full[q]] = ln[q];
+          }
+          for (size_t s = 0; s < T->ns && tex_failed < 0; s++) if ((int)lp[s].size() != B) {
+            const std::vector<const uint8_t *> &ptrs = lp[s];
+            const size_t cap = uvol_texture_bound(ew, eh, (int)ptrs.size()); outs[s].reset(new uint8_t[cap]);
+            if ((dev ? uvol_encode_texture_segment_dev : uvol_encode_texture_segment)(tctxs[g], ptrs.data(), (int)ptrs.size(), ew, eh, outs[s].get(), cap, &lens[s]) != UVOL_OK) fail(starts[s0 + s], uvol_last_error(tctxs[g]));
+          }
+        };
         std::vector<std::unique_ptr<uint8_t[]>> outs(T->ns); std::vector<size_t> lens(T->ns, 0);
-        // full segments: one batched call; segments with fewer layers: one call each
-        std::vector<size_t> full; for (size_t s = 0; s < T->ns; s++) if ((int)T->imgs[s].size() == B) full.push_back(s);
-        const std::vector<std::vector<const uint8_t *>> &dptr = T->dptr;
-        if (!full.empty()) {
-          std::vector<const uint8_t *> ptrs; std::vector<uint8_t *> op; std::vector<size_t> caps, ln(full.size(), 0);
-          for (size_t s : full) { for (size_t k = 0; k < T->imgs[s].size(); k++) ptrs.push_back(T->dev ? dptr[s][k] : T->imgs[s][k].rgba.data()); const size_t cap = uvol_texture_bound(w, h, B); outs[s].reset(new uint8_t[cap]); op.push_back(outs[s].get()); caps.push_back(cap); }
-          if ((T->dev ? uvol_encode_texture_segments_dev : uvol_encode_texture_segments)(tctxs[g], ptrs.data(), (int)full.size(), B, w, h, op.data(), caps.data(), ln.data()) != UVOL_OK) { fail(starts[s0 + full[0]], uvol_last_error(tctxs[g])); break; }
-          for (size_t q = 0; q < full.size(); q++) lens[full[q]] = ln[q];
-        }
-        for (size_t s = 0; s < T->ns && tex_failed < 0; s++) if ((int)T->imgs[s].size() != B) {
-          std::vector<const uint8_t *> ptrs; for (size_t k = 0; k < T->imgs[s].size(); k++) ptrs.push_back(T->dev ? dptr[s][k] : T->imgs[s][k].rgba.data());
-          const size_t cap = uvol_texture_bound(w, h, (int)ptrs.size()); outs[s].reset(new uint8_t[cap]);
-          if ((T->dev ? uvol_encode_texture_segment_dev : uvol_encode_texture_segment)(tctxs[g], ptrs.data(), (int)ptrs.size(), w, h, outs[s].get(), cap, &lens[s]) != UVOL_OK) fail(starts[s0 + s], uvol_last_error(tctxs[g]));
-        }
+        std::vector<std::vector<const uint8_t *>> layers(T->ns);
+        for (size_t s = 0; s < T->ns; s++) for (size_t k = 0; k < T->imgs[s].size(); k++) layers[s].push_back(T->dev ? T->dptr[s][k] : T->imgs[s][k].rgba.data());
+        encode_set(layers, T->dev, w, h, outs, lens);
         if (g_timing) std::fprintf(stderr, "[uvolenc-timing] tex batch s0=%zu: next batch loaded + its un-filter queued %.0f ms, encode (+prepare) %.0f\n", s0, tw1 - tw0, now_ms() - tw1);
         if (tex_failed >= 0) break;
         std::atomic<int> wbad{-1};
         parallel_for(T->ns, tex_ingest, [&](size_t s) { char name[64]; std::snprintf(name, sizeof name, "%0*d.ktx2", pad, (starts[s0 + s] - cfg.ktx2_first_file) / B); if (!write_file(join(tex_dir, name), outs[s].get(), lens[s])) wbad = starts[s0 + s]; });
         if (wbad >= 0) { tex_failed = wbad.load(); break; }
+        // --texture-ladder: every rung downscales this batch's layers on the GPU - the device layers of the un-filter, or the host images -,
+        // encodes them through the same entry points (short last segments and --uastc included) and writes its own directory
+        std::vector<std::unique_ptr<uint8_t[]>> eouts; std::vector<size_t> elens; uint32_t ew = w, eh = h;      // the segments the etc2 target is transcoded from
+        for (size_t r = 0; r < ladder.size() && tex_failed < 0; r++) {
+          const uint32_t f = (uint32_t)ladder[r], rw = (w + f - 1) / f, rh = (h + f - 1) / f;
+          std::vector<const uint8_t *> in; for (auto &seg : layers) for (const uint8_t *p : seg) in.push_back(p);
+          std::vector<const uint8_t *> small(in.size(), nullptr);
+          if (uvol_downscale_rgba_batch_dev(tctxs[g], in.data(), (int)in.size(), w, h, T->dev ? 1 : 0, (int)f, (int)(r & 1), small.data()) != UVOL_OK) { fail(starts[s0], uvol_last_error(tctxs[g])); break; }
+          std::vector<std::vector<const uint8_t *>> rl(T->ns); size_t q = 0;
+          for (size_t s = 0; s < T->ns; s++) for (size_t k = 0; k < layers[s].size(); k++) rl[s].push_back(small[q++]);
+          std::vector<std::unique_ptr<uint8_t[]>> routs(T->ns); std::vector<size_t> rlens(T->ns, 0);
+          encode_set(rl, true, rw, rh, routs, rlens);
+          if (tex_failed >= 0) break;
+          const std::string rdir = rung_dir(rw, rh);
+          if (!make_dirs(rdir)) { std::printf("❌ cannot create %s\n", rdir.c_str()); tex_failed = starts[s0]; break; }
+          std::atomic<int> rbad{-1};
+          parallel_for(T->ns, tex_ingest, [&](size_t s) { char name[64]; std::snprintf(name, sizeof name, "%0*d.ktx2", pad, (starts[s0 + s] - cfg.ktx2_first_file) / B); if (!write_file(join(rdir, name), routs[s].get(), rlens[s])) rbad = starts[s0 + s]; });
+          if (rbad >= 0) { tex_failed = rbad.load(); break; }
+          if (want_etc2 && (int)f == etc2_scale) { eouts = std::move(routs); elens = std::move(rlens); ew = rw; eh = rh; }
+        }
+        if (tex_failed >= 0) break;
         // raw `etc2` target (src/V2/player.ts:338-356): every layer of the segments just written, transcoded on the GPU to ETC1 blocks
         // (valid ETC2 RGB), one .etc2 file per FRAME (the player builds one CompressedTexture per file)
         if (want_etc2) {
-          const size_t nbk = (size_t)((w + 3) / 4) * ((h + 3) / 4) * 8;
+          const size_t nbk = (size_t)((ew + 3) / 4) * ((eh + 3) / 4) * 8;
           for (size_t s = 0; s < T->ns && tex_failed < 0; s++) {
             const size_t nl = T->imgs[s].size();
             std::vector<std::unique_ptr<uint8_t[]>> blk(nl); std::vector<uint8_t *> bp(nl);
             for (size_t l = 0; l < nl; l++) { blk[l].reset(new uint8_t[nbk]); bp[l] = blk[l].get(); }
-            const uint8_t *fp = outs[s].get(); const size_t fl = lens[s];
+            const uint8_t *fp = etc2_scale == 1 ? outs[s].get() : eouts[s].get(); const size_t fl = etc2_scale == 1 ? lens[s] : elens[s];      // (--etc2-scale: that rung's segments)
             if (uvol_transcode_texture_segments_etc1(tctxs[g], &fp, &fl, 1, bp.data(), nbk, 0) != UVOL_OK) { fail(starts[s0 + s], uvol_last_error(tctxs[g])); break; }
             for (size_t l = 0; l < nl; l++) { char name[64]; std::snprintf(name, sizeof name, "%0*d.etc2", pad, starts[s0 + s] - cfg.ktx2_first_file + (int)l); if (!write_file(join(etc_dir, name), bp[l], nbk)) { tex_failed = starts[s0 + s]; break; } }
             etc2_frames += (long)nl;
@@ -462,7 +509,10 @@ int main(int argc, char **argv) {
     }
   } else std::printf("💡 Audio file not supplied, Skipping duration check...\n");
   if (!tex_w) { std::vector<uint8_t> k; std::string d = dirname_of(cfg.ktx2_files_path); for (auto &f : list_dir(d)) if (match_pattern_lenient(basename_of(cfg.ktx2_files_path), f)) { if (read_file(join(d, f), k) && k.size() >= 28) { std::memcpy(&tex_w, &k[20], 4); std::memcpy(&tex_h, &k[24], 4); } break; } }
-  const std::string man = json_dump(manifest_player(cfg, fc.geometry_frames, fc.texture_segments, tex_w, tex_h, pad, want_etc2 ? etc2_frames.load() : 0));
+  std::vector<TexRung> rungs; for (int f : ladder) rungs.push_back(TexRung{ (tex_w + (uint32_t)f - 1) / (uint32_t)f, (tex_h + (uint32_t)f - 1) / (uint32_t)f });
+  const uint32_t es = (uint32_t)etc2_scale;
+  const std::string man = json_dump(manifest_player(cfg, fc.geometry_frames, fc.texture_segments, tex_w, tex_h, pad, want_etc2 ? etc2_frames.load() : 0, rungs,
+                                                    es > 1 ? (tex_w + es - 1) / es : 0, es > 1 ? (tex_h + es - 1) / es : 0));
   const std::string mpath = join(cfg.output_directory, "uvol.json");
   if (!write_file(mpath, man.data(), man.size())) return 1;
   if (encpy) { const std::string m2 = json_dump(manifest_encoder_py(cfg, fc.geometry_frames, fc.texture_segments, "geometry_draco/" + std::string((size_t)pad, '#') + ".drc", "texture_ktx2_baseColor_default/" + std::string((size_t)pad, '#') + ".ktx2"));

@@ -69,7 +69,7 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_profile_get", "uvol_encode_texture_segments_st", "uvol_transcode_texture_segments_st",
            "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status",
            "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat",
-           "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed"]
+           "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed", "uvol_downscale_rgba_batch_dev"]
 
 
 def load(path=None):
@@ -125,6 +125,7 @@ def load(path=None):
     L.uvol_unfilter_png_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.uvol_inflate_png_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.uvol_png_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]
+    L.uvol_downscale_rgba_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.uvol_parse_obj_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_int)]
     L.uvol_encode_mesh_batch_dev_out.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.uvol_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -327,6 +328,32 @@ class Codec:
         if sync and self.L.uvol_sync(self.h) != UVOL_OK:
             raise UvolError(f"uvol_sync: {self.error()}")
         return [int(p) for p in out], list(st)
+
+    def downscale_rgba_batch_dev(self, layers_or_ptrs, width, height, factor, slot=0, on_device=None):
+        """uvol_downscale_rgba_batch_dev: layers of one size, downscaled by factor 2 / 4 / 8 on the device -> list of DEVICE pointers to the
+        ceil(width / factor) x ceil(height / factor) RGBA8 layers in the context's downscale slot (valid until that slot is written again;
+        what encode_texture_segment[s]_dev takes).  layers_or_ptrs: device pointers (ints), or host images (HxWx4 uint8 arrays / bytes of
+        width * height * 4), which are uploaded.  on_device=None: device pointers when every entry is an int."""
+        items = list(layers_or_ptrs); n = len(items)
+        if on_device is None:
+            on_device = n > 0 and all(isinstance(x, int) for x in items)
+        keep = []
+        if on_device:
+            ptrs = (C.c_void_p * n)(*[int(p) if p else None for p in items])
+        else:
+            for a in items:
+                if a is None:
+                    keep.append(None); continue
+                a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+                if a.size != width * height * 4:
+                    raise ValueError("every layer must hold width * height * 4 bytes")
+                keep.append(a)
+            ptrs = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep])
+        out = (C.c_void_p * n)()
+        rc = self.L.uvol_downscale_rgba_batch_dev(self.h, ptrs, n, width, height, 1 if on_device else 0, factor, slot, out)
+        if rc != UVOL_OK:
+            raise UvolError(f"downscale_rgba_batch_dev rc={rc}: {self.error()}")
+        return [int(p) for p in out]
 
     def drc_info(self, data):
         nf, mv = C.c_uint32(), C.c_uint32()
