@@ -201,6 +201,56 @@ int uvol_png_status(uvol_ctx *ctx, int slot, int *status, int n);
 int uvol_downscale_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height,
                                   int inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
 
+/* ---- the raw `etc2` texture target from source texels (additive: uvol_abi_version stays 1) ----
+ * The player's raw `etc2` target is uncompressed block data, one file per frame at 8 bytes per 4x4 block, for the devices that cannot afford
+ * the transcoder (reference src/Interfaces.ts:19, :165-169, src/V2/player.ts:208-222, :338-356, :454-470).
+ * uvol_transcode_texture_segments_etc1 makes it by re-packing ETC1S segments: one base colour and one table per block, snapped to the
+ * segment's codebooks, at a file size that is fixed anyway.  This entry point encodes it from the SOURCE texels with a search over all of
+ * ETC1: n RGBA8 layers of width x height (rgba[i]: width * height * 4 bytes, top row first) -> blocks[i] = ceil(width / 4) * ceil(height / 4)
+ * 8-byte ETC1 blocks (valid ETC2 RGB8), raster order, the byte layout uvol_transcode_texture_segments_etc1 writes; ONE kernel launch for the
+ * batch.  Texels are fetched as the texture encoder fetches them: the context's y_flip applies, edges are replicated for partial blocks,
+ * px[4 y + x]; alpha is ignored (the player uploads RGB_ETC2_Format).
+ *
+ * The encoding rule is this project's own, exact in integers (this text is normative; tests/etc2_direct_cases.py restates it in NumPy and
+ * is checked bit for bit).
+ * Preliminaries.  For flip f in {0, 1}, half h of texel (x, y) is x >= 2 (f = 0) or y >= 2 (f = 1).  Per half and channel:
+ *   m8 = (sum over its 8 texels + 4) >> 3, q5 = (m8 * 31 + 127) / 255, q4 = (m8 * 15 + 127) / 255.  A 5-bit base b expands to
+ *   (b << 3) | (b >> 2), a 4-bit base to b * 17.  Modifiers are those of ETC1: table t has magnitudes {2,8}, {5,17}, {9,29}, {13,42}, {18,60},
+ *   {24,80}, {33,106}, {47,183}; pixel index 0 .. 3 = +small, +large, -small, -large.
+ * Half error E(base, t): the sum over the half's 8 texels of the smallest squared RGB error among the four modified colours, each channel
+ *   clamped to 0 .. 255 before the difference is taken; each texel takes the first nearest index in the order 0 .. 3.
+ * Half search in precision P (5 or 4 bits, top value 31 or 15), starting at q = q5 or q4.
+ *   Step 1: for t = 0 .. 7, for dd in the order (0, -1, +1): the candidate is clamp(q[c] + dd, 0, top) on all three channels; a candidate
+ *     replaces the best only on strictly smaller E.
+ *   Step 2, at the best table of step 1: for c = 0 .. 2, for dd in the order (-1, +1): channel c alone is moved from the current best base;
+ *     the move is skipped if it leaves 0 .. top and accepted only on strictly smaller E.
+ *   The unrefined result is kept too: the best t at base q with dd = 0, first best.
+ * Per flip.  Individual candidate: both halves searched in 4 bits, E_ind = the sum of their errors.  Differential candidate: both halves
+ *   searched in 5 bits; if every refined delta (second - first) lies in -4 .. 3 the refined pair is used; otherwise, if the unrefined q5 pair
+ *   has all deltas in -4 .. 3, that pair with its best tables; otherwise there is none.  Differential wins when it exists and
+ *   E_diff <= E_ind.
+ * Block.  Flip 1 wins only with strictly smaller error than flip 0.  Bytes 0 .. 2: base5 << 3 | (delta & 7) (differential) or
+ *   base4 of the first half << 4 | base4 of the second (individual), R G B; byte 3: table of the first half << 5 | table of the second << 2 |
+ *   diff << 1 | flip; bytes 4 .. 7: the msb plane and the lsb plane of the pixel indices, 16 bits each, big-endian, pixel i = 4 x + y.
+ * Two properties follow: every block's squared error against its source texels is <= that of the plain ETC1 fit the UASTC transcode uses
+ * (mean colours, best table per half) on the same texels - base q with every table is among the candidates of both modes, and the fallback
+ * keeps the plain differential fit reachable -; and a differential block has 0 <= base5 + delta <= 31 in every channel, so no block falls
+ * into ETC2's T, H or planar modes.  Those three modes are NOT used: their bit layouts are in nothing this project has at hand, and it does
+ * not restate formats from memory.  Neither is there an EAC alpha form or an enqueue form.
+ *
+ * inputs_on_device: rgba[i] are device pointers (4-byte aligned; layers of a PNG ingest slot or a downscale slot are ordered behind the
+ * kernels that produce them, as the texture entry points do it); otherwise host memory, uploaded through the library's staging buffers.
+ * outputs_on_device: blocks[i] are device pointers (8-byte aligned); otherwise host memory, pageable or from uvol_host_alloc, on the paths
+ * of the transcode entry points.  layer_cap = the size of each output buffer, at least uvol_etc2_rgb_bound(width, height) =
+ * 8 * ceil(width / 4) * ceil(height / 4).
+ * Blocking: it first waits for the context's enqueued calls and returns when the blocks are complete.  UVOL_E_INVALID with a message,
+ * before anything runs: a NULL layer or output, a misaligned device pointer, width or height zero or beyond the limits of
+ * uvol_unfilter_png_batch_dev (8192 x 16384).  UVOL_E_NOSPACE: layer_cap below the bound.  n <= 0 is UVOL_OK and does nothing.  Profile
+ * groups: etc2.encode (and etc2.upload for host inputs). */
+size_t uvol_etc2_rgb_bound(uint32_t width, uint32_t height);
+int uvol_encode_etc2_rgb_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height,
+                               int inputs_on_device, uint8_t *const *blocks, size_t layer_cap, int outputs_on_device);
+
 /* GPU-resident form (SURVEY 8(b) "variants taking arrays of frames + hipStream_t"; caller-owned buffers as in
  * deprecated/encoder_legacy/codec/corto_codec.h:41-43): inputs are device pointers PRODUCED ON `producer_stream` (a hipStream_t passed
  * as void *, NULL = already complete) - the codec's kernels are ordered after the work queued on that stream so far, without a host

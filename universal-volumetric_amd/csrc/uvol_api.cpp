@@ -269,7 +269,7 @@ void uvol_ctx_destroy(uvol_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   ctx->resolve_profile();
   geo_destroy(ctx); tex_destroy(ctx); uvol_uplink_destroy(ctx);      // (the lanes' streams are synchronised and gone before the slots they read are freed)
-  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx); down_destroy(ctx);
+  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx); down_destroy(ctx); etc2_destroy(ctx);
   for (int k = 0; k < 2; k++) { if (ctx->up_pin[k]) (void)hipHostFree(ctx->up_pin[k]); if (ctx->up_ev[k]) (void)hipEventDestroy(ctx->up_ev[k]); }
   for (int k = 0; k < 2; k++) if (ctx->pin_ev[k]) (void)hipEventDestroy(ctx->pin_ev[k]);
   for (int k = 0; k < 2; k++) { if (ctx->dn_pin[k]) (void)hipHostFree(ctx->dn_pin[k]); if (ctx->dn_ev[k]) (void)hipEventDestroy(ctx->dn_ev[k]); }
@@ -302,6 +302,7 @@ int uvol_trim(uvol_ctx *ctx) {
   const int ru = tex_trim(ctx); if (rt == UVOL_OK) rt = ru;
   uvol_uplink_trim(ctx);
   down_trim(ctx);
+  etc2_trim(ctx);
   return rc != UVOL_OK ? rc : (rf != UVOL_OK ? rf : (rx != UVOL_OK ? rx : rt));
 }
 
@@ -686,6 +687,15 @@ int uvol_downscale_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int
   if (!rgba || !rgba_dev_out) { ctx->set_error("uvol_downscale_rgba_batch_dev: %s is NULL", !rgba ? "rgba" : "rgba_dev_out"); return UVOL_E_INVALID; }
   (void)hipSetDevice(ctx->device);
   return down_rgba_batch(ctx, rgba, n, width, height, inputs_on_device != 0, factor, slot, rgba_dev_out);
+}
+size_t uvol_etc2_rgb_bound(uint32_t width, uint32_t height) { return (size_t)8 * ((width + 3u) / 4u) * ((height + 3u) / 4u); }
+int uvol_encode_etc2_rgb_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height, int inputs_on_device, uint8_t *const *blocks, size_t layer_cap, int outputs_on_device) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx) return UVOL_E_INVALID;
+  if (n <= 0) return UVOL_OK;
+  if (!rgba || !blocks) { ctx->set_error("uvol_encode_etc2_rgb_batch: %s is NULL", !rgba ? "rgba" : "blocks"); return UVOL_E_INVALID; }
+  (void)hipSetDevice(ctx->device);
+  return etc2_rgb_batch(ctx, rgba, n, width, height, inputs_on_device != 0, blocks, layer_cap, outputs_on_device != 0);
 }
 int uvol_png_status(uvol_ctx *ctx, int slot, int *status, int n) {
   if (!ctx) return UVOL_E_INVALID;

@@ -158,6 +158,7 @@ struct UastcState;   // UASTC texture mode (tex_uastc.hip)
 struct ObjState;     // OBJ text ingest on the device (obj_ingest.hip)
 struct PngState;     // PNG scanlines un-filtered on the device (png_ingest.hip)
 struct DownState;    // RGBA layers downscaled on the device (tex_downscale.hip)
+struct Etc2State;    // RGBA layers encoded to full ETC1 blocks (tex_etc2.hip)
 
 struct uvol_ctx {
   int device = 0;
@@ -176,6 +177,7 @@ struct uvol_ctx {
   ObjState *obj = nullptr;
   PngState *png = nullptr;
   DownState *down = nullptr;      // created by the first uvol_downscale_rgba_batch_dev
+  Etc2State *etc2 = nullptr;      // created by the first uvol_encode_etc2_rgb_batch
   // enqueue form of the ABI (uvol_*_async + uvol_sync): calls run in order on this context's worker thread
   struct AsyncQ {
     std::mutex m; std::condition_variable cv_work, cv_idle; std::deque<std::function<int()>> q; std::thread th; bool busy = false, stop = false; int first_err = 0; char err[512] = {0};
@@ -271,6 +273,10 @@ int png_status(uvol_ctx *ctx, int slot, int *status, int n);
 int down_rgba_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
 void down_trim(uvol_ctx *ctx);
 void down_destroy(uvol_ctx *ctx);
+// uvol_encode_etc2_rgb_batch (tex_etc2.hip); the state is created by the first call
+int etc2_rgb_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, uint8_t *const *blocks, size_t layer_cap, bool outputs_on_device);
+void etc2_trim(uvol_ctx *ctx);
+void etc2_destroy(uvol_ctx *ctx);
 int uastc_create(uvol_ctx *ctx);
 void uastc_destroy(uvol_ctx *ctx);
 #define UASTC_PROBE_SUPERCOMPRESSED (-10)      /* a UASTC .ktx2 (DFD colour model 166) whose level data are Zstandard-supercompressed */

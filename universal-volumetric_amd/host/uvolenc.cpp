@@ -4,7 +4,7 @@
 // player reads (src/Interfaces.ts:75-132, src/V2/player.ts:141-174).
 //
 //   uvolenc project-config.json [--gpus N] [--device D] [--batch-frames F] [--ingest-threads T] [--targets ktx2[,etc2]] [--uastc] [--material-seams] [--device-inflate [--tex-batch-frames F]]
-//                               [--texture-ladder F[,F...] [--etc2-scale F]] [--force] [--encoder-py-manifest]
+//                               [--texture-ladder F[,F...] [--etc2-scale F]] [--etc2-direct] [--force] [--encoder-py-manifest]
 //   --targets   texture targets to write (src/Interfaces.ts:19 TextureFileFormat): `ktx2` always; `etc2` adds one raw ETC2 RGB
 //               (ETC1-subset) block image per frame, transcoded on the GPU from the ETC1S segments, and a second target in the manifest
 //   --texture-ladder   reduced-resolution tiers (src/Interfaces.ts:41-73: every texture target has its own `resolution`): for every factor F of
@@ -13,6 +13,9 @@
 //               `ktx2_<w>x<h>` per rung behind `ktx2` and `etc2` (the stock player's choice is unchanged; a host application picks a tier by name)
 //   --etc2-scale F   1 (default) or a factor of the ladder: the raw `etc2` target is transcoded from THAT rung's segments and carries its resolution
 //               (the tier the stock player picks on devices with the ETC extension, which cannot afford full-size frames either)
+//   --etc2-direct   the raw `etc2` target is ENCODED from the batch's layers in HBM (with --etc2-scale F: from that rung's downscaled layers) by a
+//               search over all of ETC1 (uvol_encode_etc2_rgb_batch) instead of transcoded from the segments: same file names, sizes and manifest,
+//               better blocks; the target is then independent of the segment encoder, so it may be combined with --uastc
 //   --uastc     the KTX2 files carry UASTC LDR 4x4 blocks (`basisu -uastc`) instead of ETC1S/BasisLZ
 //   --material-seams   (or UVOL_MATERIAL_SEAMS=1) frames whose `usemtl` materials meet at shared vertices are written with the material
 //               attribute as a corner attribute instead of without it
@@ -66,7 +69,7 @@ int main(int argc, char **argv) {
   }
   const auto t_start = std::chrono::steady_clock::now();
   { const char *e = std::getenv("UVOL_TIMING"); g_timing = e && *e == '1'; }
-  int n_gpus = 1, device0 = 0, frames_per_batch = 32, ingest_threads = 0; bool force = false, encpy = false, want_etc2 = false, uastc = false, host_obj = false, host_png = false, dev_inflate = false, pinned_text = false, material_seams = false; int tex_batch_frames = 0;
+  int n_gpus = 1, device0 = 0, frames_per_batch = 32, ingest_threads = 0; bool force = false, encpy = false, want_etc2 = false, uastc = false, host_obj = false, host_png = false, dev_inflate = false, pinned_text = false, material_seams = false, etc2_direct = false; int tex_batch_frames = 0;
   std::vector<int> ladder; int etc2_scale = 1;      // --texture-ladder: the rungs' factors in the order given; --etc2-scale
   { const char *e = std::getenv("UVOL_MATERIAL_SEAMS"); material_seams = e && *e == '1'; }      // (= --material-seams)
   for (int i = 2; i < argc; i++) {
@@ -83,6 +86,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--uastc")) uastc = true;
     else if (!std::strcmp(argv[i], "--material-seams")) material_seams = true;      // frames whose materials meet at shared vertices keep their material attribute (uvol_params.material_seams)
     else if (!std::strcmp(argv[i], "--encoder-py-manifest")) encpy = true;
+    else if (!std::strcmp(argv[i], "--etc2-direct")) etc2_direct = true;
     else if (!std::strcmp(argv[i], "--etc2-scale") && i + 1 < argc) etc2_scale = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--texture-ladder") && i + 1 < argc) {
       const std::string t = argv[++i]; size_t a = 0;
@@ -104,7 +108,8 @@ int main(int argc, char **argv) {
       }
     }
   }
-  if (want_etc2 && uastc) { std::printf("❌ the etc2 target is transcoded from ETC1S segments; it cannot be combined with --uastc\n"); return 1; }
+  if (want_etc2 && uastc && !etc2_direct) { std::printf("❌ the etc2 target is transcoded from ETC1S segments; it cannot be combined with --uastc\n"); return 1; }
+  if (etc2_direct && !want_etc2) { std::printf("❌ --etc2-direct needs --targets etc2 (it chooses how that target is made)\n"); return 1; }
   if (etc2_scale != 1 && std::find(ladder.begin(), ladder.end(), etc2_scale) == ladder.end()) { std::printf("❌ --etc2-scale takes 1 or a factor of --texture-ladder (got %d)\n", etc2_scale); return 1; }
   std::vector<uint8_t> raw; if (!read_file(argv[1], raw)) { std::printf("❌ cannot read %s\n", argv[1]); return 1; }
   Config cfg; std::string err;
@@ -429,6 +434,19 @@ int main(int argc, char **argv) {
             if ((dev ? uvol_encode_texture_segment_dev : uvol_encode_texture_segment)(tctxs[g], ptrs.data(), (int)ptrs.size(), ew, eh, outs[s].get(), cap, &lens[s]) != UVOL_OK) fail(starts[s0 + s], uvol_last_error(tctxs[g]));
           }
         };
+        // --etc2-direct: the raw `etc2` target searched from layers lp[s][k] (device or host memory) of ew x eh, one .etc2 file per frame
+        auto direct_etc2 = [&](const std::vector<std::vector<const uint8_t *>> &lp, bool dev, uint32_t ew, uint32_t eh) {
+          const size_t nbk = uvol_etc2_rgb_bound(ew, eh);
+          std::vector<const uint8_t *> in; std::vector<int> frame;
+          for (size_t s = 0; s < T->ns; s++) for (size_t k = 0; k < lp[s].size(); k++) { in.push_back(lp[s][k]); frame.push_back(starts[s0 + s] - cfg.ktx2_first_file + (int)k); }
+          std::vector<std::unique_ptr<uint8_t[]>> blk(in.size()); std::vector<uint8_t *> bp(in.size());
+          for (size_t l = 0; l < in.size(); l++) { blk[l].reset(new uint8_t[nbk]); bp[l] = blk[l].get(); }
+          if (uvol_encode_etc2_rgb_batch(tctxs[g], in.data(), (int)in.size(), ew, eh, dev ? 1 : 0, bp.data(), nbk, 0) != UVOL_OK) { fail(starts[s0], uvol_last_error(tctxs[g])); return; }
+          std::atomic<int> ebad{-1};
+          parallel_for(in.size(), tex_ingest, [&](size_t l) { char name[64]; std::snprintf(name, sizeof name, "%0*d.etc2", pad, frame[l]); if (!write_file(join(etc_dir, name), bp[l], nbk)) ebad = frame[l] + cfg.ktx2_first_file; });
+          if (ebad >= 0) { tex_failed = ebad.load(); return; }
+          etc2_frames += (long)in.size();
+        };
         std::vector<std::unique_ptr<uint8_t[]>> outs(T->ns); std::vector<size_t> lens(T->ns, 0);
         std::vector<std::vector<const uint8_t *>> layers(T->ns);
         for (size_t s = 0; s < T->ns; s++) for (size_t k = 0; k < T->imgs[s].size(); k++) layers[s].push_back(T->dev ? T->dptr[s][k] : T->imgs[s][k].rgba.data());
@@ -438,6 +456,7 @@ int main(int argc, char **argv) {
         std::atomic<int> wbad{-1};
         parallel_for(T->ns, tex_ingest, [&](size_t s) { char name[64]; std::snprintf(name, sizeof name, "%0*d.ktx2", pad, (starts[s0 + s] - cfg.ktx2_first_file) / B); if (!write_file(join(tex_dir, name), outs[s].get(), lens[s])) wbad = starts[s0 + s]; });
         if (wbad >= 0) { tex_failed = wbad.load(); break; }
+        if (want_etc2 && etc2_direct && etc2_scale == 1) { direct_etc2(layers, T->dev, w, h); if (tex_failed >= 0) break; }
         // --texture-ladder: every rung downscales this batch's layers on the GPU - the device layers of the un-filter, or the host images -,
         // encodes them through the same entry points (short last segments and --uastc included) and writes its own directory
         std::vector<std::unique_ptr<uint8_t[]>> eouts; std::vector<size_t> elens; uint32_t ew = w, eh = h;      // the segments the etc2 target is transcoded from
@@ -448,6 +467,7 @@ int main(int argc, char **argv) {
           if (uvol_downscale_rgba_batch_dev(tctxs[g], in.data(), (int)in.size(), w, h, T->dev ? 1 : 0, (int)f, (int)(r & 1), small.data()) != UVOL_OK) { fail(starts[s0], uvol_last_error(tctxs[g])); break; }
           std::vector<std::vector<const uint8_t *>> rl(T->ns); size_t q = 0;
           for (size_t s = 0; s < T->ns; s++) for (size_t k = 0; k < layers[s].size(); k++) rl[s].push_back(small[q++]);
+          if (want_etc2 && etc2_direct && (int)f == etc2_scale) { direct_etc2(rl, true, rw, rh); if (tex_failed >= 0) break; }      // (while the rung's layers are in their slot)
           std::vector<std::unique_ptr<uint8_t[]>> routs(T->ns); std::vector<size_t> rlens(T->ns, 0);
           encode_set(rl, true, rw, rh, routs, rlens);
           if (tex_failed >= 0) break;
@@ -461,7 +481,7 @@ int main(int argc, char **argv) {
         if (tex_failed >= 0) break;
         // raw `etc2` target (src/V2/player.ts:338-356): every layer of the segments just written, transcoded on the GPU to ETC1 blocks
         // (valid ETC2 RGB), one .etc2 file per FRAME (the player builds one CompressedTexture per file)
-        if (want_etc2) {
+        if (want_etc2 && !etc2_direct) {
           const size_t nbk = (size_t)((ew + 3) / 4) * ((eh + 3) / 4) * 8;
           for (size_t s = 0; s < T->ns && tex_failed < 0; s++) {
             const size_t nl = T->imgs[s].size();

@@ -69,7 +69,8 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_profile_get", "uvol_encode_texture_segments_st", "uvol_transcode_texture_segments_st",
            "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status",
            "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat",
-           "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed", "uvol_downscale_rgba_batch_dev"]
+           "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed", "uvol_downscale_rgba_batch_dev",
+           "uvol_etc2_rgb_bound", "uvol_encode_etc2_rgb_batch"]
 
 
 def load(path=None):
@@ -126,6 +127,9 @@ def load(path=None):
     L.uvol_inflate_png_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
     L.uvol_png_status.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int]
     L.uvol_downscale_rgba_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+    if hasattr(L, "uvol_encode_etc2_rgb_batch"):      # (a build that predates the entry point still loads: tools/etc2_direct_timing.py may time one beside this build)
+        L.uvol_etc2_rgb_bound.argtypes = [C.c_uint32, C.c_uint32]; L.uvol_etc2_rgb_bound.restype = C.c_size_t
+        L.uvol_encode_etc2_rgb_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_int]
     L.uvol_parse_obj_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_int)]
     L.uvol_encode_mesh_batch_dev_out.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.uvol_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -354,6 +358,38 @@ class Codec:
         if rc != UVOL_OK:
             raise UvolError(f"downscale_rgba_batch_dev rc={rc}: {self.error()}")
         return [int(p) for p in out]
+
+    def encode_etc2_rgb_batch(self, layers_or_ptrs, width, height, on_device=None, out_dev_ptrs=None, layer_cap=None):
+        """uvol_encode_etc2_rgb_batch: RGBA8 layers of one size -> full ETC1 blocks (valid ETC2 RGB8) searched from the source texels, one launch
+        for the batch.  layers_or_ptrs: device pointers (ints), or host images (HxWx4 uint8 arrays / bytes of width * height * 4), which are
+        uploaded; on_device=None: device pointers when every entry is an int.  Returns a list of [by, bx, 8] uint8 arrays - or, with
+        out_dev_ptrs (one 8-byte aligned device buffer of uvol_etc2_rgb_bound bytes per layer), writes there and returns None.  layer_cap:
+        the size of each output buffer when it is not the bound."""
+        items = list(layers_or_ptrs); n = len(items)
+        if on_device is None:
+            on_device = n > 0 and all(isinstance(x, int) for x in items)
+        keep = []
+        if on_device:
+            ptrs = (C.c_void_p * n)(*[int(p) if p else None for p in items])
+        else:
+            for a in items:
+                if a is None:
+                    keep.append(None); continue
+                a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+                if a.size != width * height * 4:
+                    raise ValueError("every layer must hold width * height * 4 bytes")
+                keep.append(a)
+            ptrs = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep])
+        bx, by = (width + 3) // 4, (height + 3) // 4
+        cap = bx * by * 8 if layer_cap is None else layer_cap
+        if out_dev_ptrs is not None:
+            outs = None; op = (C.c_void_p * n)(*[int(p) if p else None for p in out_dev_ptrs])
+        else:
+            outs = [np.empty((by, bx, 8), dtype=np.uint8) for _ in range(n)]; op = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
+        rc = self.L.uvol_encode_etc2_rgb_batch(self.h, ptrs, n, width, height, 1 if on_device else 0, op, cap, 0 if outs is not None else 1)
+        if rc != UVOL_OK:
+            raise UvolError(f"encode_etc2_rgb_batch rc={rc}: {self.error()}")
+        return outs
 
     def drc_info(self, data):
         nf, mv = C.c_uint32(), C.c_uint32()
