@@ -10,8 +10,10 @@
 //                     (macroblock endpoint predictors + RLE, delta endpoints, selector history) -> per-block indices;
 //                     P-frame skips copy the previous slice, so the slices of a segment are decoded in order
 //   k_tdec_unpack     1 thread / block: (colour5, intensity table, 16 selectors) -> 16 RGBA8 texels, 16-byte row stores
+//                     (or one of the block targets: k_tdec_etc1 / _etc2a / _bc13 / _bc7; the block formats are stated in tex_blocks.hpp)
 // Bound: the VLC walk is serial per segment (latency / scalar ALU), the unpack is HBM-write bound (4 B per texel).
 #include "uvol_common.hpp"
+#include "tex_blocks.hpp"
 
 #define TD_MAX_LAYERS 64
 #define TD_MAX_SYMS 16512          // >= TEX_MAX_CODEBOOK + history + RLE symbol
@@ -319,206 +321,113 @@ __global__ void __launch_bounds__(1024) k_tdec_slices_pipe(TexDecJob *jobs) {
   if (tid == 0 && s_fail) J.status = s_fail;
 }
 
-// ---- K3: unpack, one thread per (block, layer, segment) ----
+// ---- K3 and its variants, one thread per (block, layer, segment): what they share ----
+// of the job J of this thread's segment: its layer and block, o = the block's index in the colour slice's ei / si (slice layer << ashift;
+// k_tdec_etc1 only sees opaque files, where that is the layer itself); false: nothing to do (a failed segment, or past the end)
+__device__ __forceinline__ bool tdec_begin(const TexDecJob &J, uint32_t &layer, uint32_t &b, size_t &o) {
+  if (J.status != 0) return false;
+  layer = blockIdx.y; b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (layer >= J.layers || b >= J.bx * J.by) return false;
+  o = (size_t)(layer << J.ashift) * J.bx * J.by + b;
+  return true;
+}
+// (endpoint r5 g5 b5 table, selector word) of the colour slice's block o, and of the alpha slice's (files with alpha slices only)
+__device__ __forceinline__ const uint8_t *tdec_fetch(const TexDecJob &J, size_t o, uint32_t &sel) { sel = J.selectors[J.si[o]]; return J.endpoints + 4 * (size_t)J.ei[o]; }
+__device__ __forceinline__ const uint8_t *tdec_fetch_alpha(const TexDecJob &J, size_t o, uint32_t &asel) { return tdec_fetch(J, o + (size_t)J.bx * J.by, asel); }
+// the four colours of an ETC1S block, dark to bright: the 5-bit base widened, plus the intensity table, clamped per channel
+__device__ __forceinline__ void tdec_colours(const uint8_t *e, int col[4][3]) {
+  int mod[4]; etc1s_mods(e[3] & 7, mod);
+  for (int c = 0; c < 3; c++) for (int k = 0; k < 4; k++) col[k][c] = t_clampi(t_expand5(e[c]) + mod[k], 0, 255);
+}
+// the four levels of an alpha-slice block: its green channel (what the basis transcoder takes)
+__device__ __forceinline__ void tdec_levels(const uint8_t *ae, int al[4]) {
+  int mod[4]; etc1s_mods(ae[3] & 7, mod);
+  for (int k = 0; k < 4; k++) al[k] = t_clampi(t_expand5(ae[1]) + mod[k], 0, 255);
+}
+// bit k: some texel has selector k; the lowest / highest selector in use (a block of one selector: equal)
+__device__ __forceinline__ uint32_t tdec_used(uint32_t sel) { uint32_t used = 0; for (int i = 0; i < 16; i++) used |= 1u << ((sel >> (2 * i)) & 3u); return used; }
+__device__ __forceinline__ void tdec_used_range(uint32_t sel, int &klo, int &khi) {
+  const uint32_t used = tdec_used(sel);
+  klo = 0; khi = 3;
+  while (!((used >> klo) & 1u)) klo++;
+  while (!((used >> khi) & 1u)) khi--;
+}
+__device__ __forceinline__ uint32_t tdec_pick(const uint32_t v[4], uint32_t sel, int i) { return v[(sel >> (2 * i)) & 3u]; }      // the entry texel i selects
+
+// ---- K3: unpack to RGBA8 ----
 __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_unpack(TexDecJob *jobs) {
-  TexDecJob &J = jobs[blockIdx.z];
-  if (J.status != 0) return;
-  const uint32_t layer = blockIdx.y, b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
-  const uint32_t bx = J.bx, by = J.by, W = J.width, H = J.height;
-  if (layer >= J.layers || b >= bx * by) return;
-  const int INTEN[8][4] = { {-8, -2, 2, 8}, {-17, -5, 5, 17}, {-29, -9, 9, 29}, {-42, -13, 13, 42}, {-60, -18, 18, 60}, {-80, -24, 24, 80}, {-106, -33, 33, 106}, {-183, -47, 47, 183} };
-  const uint32_t X = b % bx, Y = b / bx;
-  const size_t o = (size_t)(layer << J.ashift) * bx * by + b;
-  const uint8_t *e = J.endpoints + 4 * (size_t)J.ei[o]; const uint32_t sel = J.selectors[J.si[o]];
-  int base[3]; for (int c = 0; c < 3; c++) base[c] = (e[c] << 3) | (e[c] >> 2);
-  const int t = e[3];
-  // alpha: the block of the image's alpha slice, green channel (what the basis transcoder takes)
-  const uint8_t *ae = J.ashift ? J.endpoints + 4 * (size_t)J.ei[o + (size_t)bx * by] : e; const uint32_t asel = J.ashift ? J.selectors[J.si[o + (size_t)bx * by]] : 0u;
-  const int abase = (ae[1] << 3) | (ae[1] >> 2), at = ae[3];
-  uint8_t *out = J.out[layer];
+  const TexDecJob &J = jobs[blockIdx.z];
+  uint32_t layer, b; size_t o; if (!tdec_begin(J, layer, b, o)) return;
+  const uint32_t X = b % J.bx, Y = b / J.bx;
+  uint32_t sel, asel = 0; int col[4][3], al[4] = { 255, 255, 255, 255 };
+  tdec_colours(tdec_fetch(J, o, sel), col);
+  if (J.ashift) tdec_levels(tdec_fetch_alpha(J, o, asel), al);
+  uint32_t rgb[4], a[4];
+  for (int k = 0; k < 4; k++) { rgb[k] = (uint32_t)col[k][0] | ((uint32_t)col[k][1] << 8) | ((uint32_t)col[k][2] << 16); a[k] = (uint32_t)al[k] << 24; }
   for (int y = 0; y < 4; y++) {
-    const uint32_t py = Y * 4 + (uint32_t)y; if (py >= H) break;
+    const uint32_t py = Y * 4 + (uint32_t)y; if (py >= J.height) break;
     uint32_t px4[4];
-    for (int x = 0; x < 4; x++) {
-      const int d = INTEN[t][(sel >> (8 * y + 2 * x)) & 3];
-      int r = base[0] + d, g = base[1] + d, bb = base[2] + d;
-      r = r < 0 ? 0 : (r > 255 ? 255 : r); g = g < 0 ? 0 : (g > 255 ? 255 : g); bb = bb < 0 ? 0 : (bb > 255 ? 255 : bb);
-      int a = 255;
-      if (J.ashift) { a = abase + INTEN[at][(asel >> (8 * y + 2 * x)) & 3]; a = a < 0 ? 0 : (a > 255 ? 255 : a); }
-      px4[x] = (uint32_t)r | ((uint32_t)g << 8) | ((uint32_t)bb << 16) | ((uint32_t)a << 24);
-    }
-    uint32_t *row = reinterpret_cast<uint32_t *>(out + 4 * ((size_t)py * W + X * 4));
-    if (X * 4 + 3 < W && (W & 3) == 0) *reinterpret_cast<uint4 *>(row) = make_uint4(px4[0], px4[1], px4[2], px4[3]);
-    else for (int x = 0; x < 4; x++) if (X * 4 + (uint32_t)x < W) row[x] = px4[x];
+    for (int x = 0; x < 4; x++) px4[x] = tdec_pick(rgb, sel, 4 * y + x) | tdec_pick(a, asel, 4 * y + x);
+    t_store_row4(J.out[layer] + 4 * (size_t)py * J.width, J.width, X, px4);
   }
 }
 
-// ---- K3': ETC1 target (the `etc2` raw-texture family of the player, reference src/Interfaces.ts:19, src/V2/player.ts:338-356):
-// every ETC1S block IS an ETC1 block — differential mode with a zero delta, both sub-blocks on the same intensity table —
-// so the transcode is a re-pack of (colour5, table, selectors) into the 8-byte block, one thread per block.
-// Block bytes: R5|dR3, G5|dG3, B5|dB3, table1(3)|table2(3)|diff(1)|flip(1), then pixel-index MSB and LSB planes (16 bits each,
-// big-endian, pixel i = 4 * x + y); ETC1S selector 0..3 (dark -> bright) maps to the ETC1 index {3, 2, 0, 1}.
+// ---- K3': ETC1 target (the `etc2` raw-texture family of the player, reference src/Interfaces.ts:19, src/V2/player.ts:338-356): the
+// re-pack (etc1_repack) of an opaque file's blocks; the host refuses a file with alpha slices.
 __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_etc1(TexDecJob *jobs) {
-  TexDecJob &J = jobs[blockIdx.z];
-  if (J.status != 0) return;
-  const uint32_t layer = blockIdx.y, b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
-  if (layer >= J.layers || b >= J.bx * J.by) return;
-  const size_t o = (size_t)layer * J.bx * J.by + b;
-  const uint8_t *e = J.endpoints + 4 * (size_t)J.ei[o]; const uint32_t sel = J.selectors[J.si[o]];
-  uint32_t msb = 0, lsb = 0;
-  for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) {
-    const uint32_t s2 = (sel >> (8 * y + 2 * x)) & 3u, idx = s2 == 0 ? 3u : (s2 == 1 ? 2u : (s2 == 2 ? 0u : 1u));
-    const int i = 4 * x + y;
-    msb |= (idx >> 1) << i; lsb |= (idx & 1u) << i;
-  }
-  const uint32_t t = e[3];
-  uint8_t *out = J.out[layer] + 8 * (size_t)b;
-  out[0] = (uint8_t)(e[0] << 3); out[1] = (uint8_t)(e[1] << 3); out[2] = (uint8_t)(e[2] << 3);
-  out[3] = (uint8_t)((t << 5) | (t << 2) | 2u);
-  out[4] = (uint8_t)(msb >> 8); out[5] = (uint8_t)msb; out[6] = (uint8_t)(lsb >> 8); out[7] = (uint8_t)lsb;
+  const TexDecJob &J = jobs[blockIdx.z];
+  uint32_t layer, b; size_t o; if (!tdec_begin(J, layer, b, o)) return;
+  uint32_t sel; const uint8_t *e = tdec_fetch(J, o, sel);
+  etc1_store(J.out[layer] + 8 * (size_t)b, etc1_repack(e, sel));
 }
 
 // ---- K3'b: ETC2 RGBA target (ETC2_EAC RGBA8: what the stock loader asks an ETC1S file WITH alpha for on ETC2 hardware,
-// src/lib/KTX2Loader.js:672-676 transcoderFormat[1]).  16 bytes per block: an EAC alpha block, then the colour block - the same exact
-// ETC1 re-pack as above (a differential block with zero deltas is a valid ETC2 block).  The alpha block of the alpha slice has four
-// levels abase + {-a, -b, +b, +a} (green channel, clamped); EAC alpha is base + multiplier * table[j], eight levels out of 16 tables:
-// every (table, multiplier 1..15) is tried with five base values around the middle of the levels, each level takes its nearest EAC
-// level, the error is summed over the 16 pixels, the first best (table, multiplier, base ascending) wins.  Not a restatement of the
-// basis transcoder's table-driven path (its tables are not in the reference): gated by alpha PSNR against the RGBA32 decode and checked
-// block by block against the plain reference of this rule in tests/transcode_ref.py.
-// Alpha block bytes: base, multiplier << 4 | table, then 16 x 3-bit indices, pixel i = 4 * x + y, first pixel in the top bits.
-__device__ const int8_t EAC_MOD[16][8] = {
-  { -3, -6, -9, -15, 2, 5, 8, 14 }, { -3, -7, -10, -13, 2, 6, 9, 12 }, { -2, -5, -8, -13, 1, 4, 7, 12 }, { -2, -4, -6, -13, 1, 3, 5, 12 },
-  { -3, -6, -8, -12, 2, 5, 7, 11 }, { -3, -7, -9, -11, 2, 6, 8, 10 }, { -4, -7, -8, -11, 3, 6, 7, 10 }, { -3, -5, -8, -11, 2, 4, 7, 10 },
-  { -2, -6, -8, -10, 1, 5, 7, 9 }, { -2, -5, -8, -10, 1, 4, 7, 9 }, { -2, -4, -8, -10, 1, 3, 7, 9 }, { -2, -5, -7, -10, 1, 4, 6, 9 },
-  { -3, -4, -7, -10, 2, 3, 6, 9 }, { -1, -2, -3, -10, 0, 1, 2, 9 }, { -4, -6, -8, -9, 3, 5, 7, 8 }, { -3, -5, -7, -9, 2, 4, 6, 8 } };
+// src/lib/KTX2Loader.js:672-676 transcoderFormat[1]).  16 bytes per block: an EAC alpha block fitted to the four levels of the alpha
+// slice's block (eac_fit), then the ETC1 re-pack of the colour block.  Gated by alpha PSNR against the RGBA32 decode and checked block by
+// block against the plain reference of the rule in tests/transcode_ref.py.
 __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_etc2a(TexDecJob *jobs) {
-  TexDecJob &J = jobs[blockIdx.z];
-  if (J.status != 0) return;
-  const uint32_t layer = blockIdx.y, b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
-  if (layer >= J.layers || b >= J.bx * J.by) return;
-  const size_t nbk = (size_t)J.bx * J.by, o = (size_t)(layer << J.ashift) * nbk + b;
-  const int INTEN[8][4] = { {-8, -2, 2, 8}, {-17, -5, 5, 17}, {-29, -9, 9, 29}, {-42, -13, 13, 42}, {-60, -18, 18, 60}, {-80, -24, 24, 80}, {-106, -33, 33, 106}, {-183, -47, 47, 183} };
+  const TexDecJob &J = jobs[blockIdx.z];
+  uint32_t layer, b; size_t o; if (!tdec_begin(J, layer, b, o)) return;
   uint8_t *out = J.out[layer] + 16 * (size_t)b;
-  // ---- alpha half ----
-  int al[4] = { 255, 255, 255, 255 }; uint32_t asel = 0, hist[4] = { 16, 0, 0, 0 };
+  int al[4] = { 255, 255, 255, 255 }; uint32_t asel = 0, hist[4] = { 16, 0, 0, 0 };      // an opaque file: sixteen texels of level 255
   if (J.ashift) {
-    const uint8_t *ae = J.endpoints + 4 * (size_t)J.ei[o + nbk]; asel = J.selectors[J.si[o + nbk]];
-    for (int k = 0; k < 4; k++) { const int v = ((ae[1] << 3) | (ae[1] >> 2)) + INTEN[ae[3] & 7][k]; al[k] = v < 0 ? 0 : (v > 255 ? 255 : v); }
+    tdec_levels(tdec_fetch_alpha(J, o, asel), al);
     hist[0] = 0; for (int i = 0; i < 16; i++) hist[(asel >> (2 * i)) & 3u]++;
   }
-  int lo_l = 255, hi_l = 0;
-  for (int k = 0; k < 4; k++) if (hist[k]) { lo_l = al[k] < lo_l ? al[k] : lo_l; hi_l = al[k] > hi_l ? al[k] : hi_l; }
-  const int mid = (lo_l + hi_l + 1) >> 1;
-  uint32_t best = 0xffffffffu; int bt = 0, bm = 1, bb = mid;
-  for (int t = 0; t < 16 && best; t++) for (int m = 1; m < 16 && best; m++) for (int db = -2; db <= 2; db++) {
-    const int base = mid + db; if (base < 0 || base > 255) continue;
-    uint32_t err = 0;
-    for (int k = 0; k < 4; k++) if (hist[k]) {
-      int be = 1 << 30;
-      for (int j = 0; j < 8; j++) { int v = base + m * EAC_MOD[t][j]; v = v < 0 ? 0 : (v > 255 ? 255 : v); const int d = v - al[k]; be = d * d < be ? d * d : be; }
-      err += hist[k] * (uint32_t)be;
-    }
-    if (err < best) { best = err; bt = t; bm = m; bb = base; }
-  }
-  uint32_t lvl[4];
-  for (int k = 0; k < 4; k++) { int be = 1 << 30; uint32_t bj = 0; for (int j = 0; j < 8; j++) { int v = bb + bm * EAC_MOD[bt][j]; v = v < 0 ? 0 : (v > 255 ? 255 : v); const int d = v - al[k]; if (d * d < be) { be = d * d; bj = (uint32_t)j; } } lvl[k] = bj; }
-  unsigned long long bits = 0;
-  for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) { const int i = 4 * x + y; bits |= (unsigned long long)lvl[(asel >> (8 * y + 2 * x)) & 3u] << (45 - 3 * i); }
-  out[0] = (uint8_t)bb; out[1] = (uint8_t)((bm << 4) | bt);
-  for (int k = 0; k < 6; k++) out[2 + k] = (uint8_t)(bits >> (40 - 8 * k));
-  // ---- colour half: the ETC1 re-pack ----
-  const uint8_t *e = J.endpoints + 4 * (size_t)J.ei[o]; const uint32_t sel = J.selectors[J.si[o]];
-  uint32_t msb = 0, lsb = 0;
-  for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) {
-    const uint32_t s2 = (sel >> (8 * y + 2 * x)) & 3u, idx = s2 == 0 ? 3u : (s2 == 1 ? 2u : (s2 == 2 ? 0u : 1u));
-    const int i = 4 * x + y;
-    msb |= (idx >> 1) << i; lsb |= (idx & 1u) << i;
-  }
-  const uint32_t t = e[3];
-  out[8] = (uint8_t)(e[0] << 3); out[9] = (uint8_t)(e[1] << 3); out[10] = (uint8_t)(e[2] << 3);
-  out[11] = (uint8_t)((t << 5) | (t << 2) | 2u);
-  out[12] = (uint8_t)(msb >> 8); out[13] = (uint8_t)msb; out[14] = (uint8_t)(lsb >> 8); out[15] = (uint8_t)lsb;
+  int bb, bm, bt; eac_fit<4>([&](int k) { return al[k]; }, [&](int k) { return hist[k]; }, false, bb, bm, bt);      // always searched: no shortcut for a block of one level
+  uint32_t lvl[4]; for (int k = 0; k < 4; k++) lvl[k] = eac_nearest(bb, bm, bt, al[k]);
+  eac_pack(out, bb, bm, bt, [&](int i) { return tdec_pick(lvl, asel, i); });
+  uint32_t sel; const uint8_t *e = tdec_fetch(J, o, sel);
+  etc1_store(out + 8, etc1_repack(e, sel));
 }
 
 // ---- K3'c: BC1 / BC3 targets (round 5; the stock loader's `dxtSupported` row, src/lib/KTX2Loader.js:610-618: TranscoderFormat.BC1 for an
-// opaque file, BC3 for one with alpha slices - its choice where neither BPTC nor ETC2 exists).  Colour: the darkest / brightest ETC1S
-// colour the block's selectors USE, rounded to RGB565, are the endpoints of a four-colour BC1 block (palette c0, c1, (2 c0 + c1) / 3, (c0 + 2 c1) / 3: ETC1's inner
-// colours sit at 0.31 - 0.39 of the span, BC1's at 1/3); each of the four ETC1S colours takes the palette entry nearest in squared error
-// (clamping can bend the line), pixels follow their selectors.  An opaque BC1 block needs colour0 > colour1 as 16-bit numbers (otherwise
-// index 3 means transparent black): endpoints are swapped and indices remapped where needed, equal endpoints use index 0 only.  For an
+// opaque file, BC3 for one with alpha slices - its choice where neither BPTC nor ETC2 exists).  Colour: the brightest / darkest ETC1S
+// colour the block's selectors USE become colour0 / colour1 of a BC1 block (ETC1's inner colours sit at 0.31 - 0.39 of the span, BC1's at
+// 1/3); the four ETC1S colours are mapped to palette entries (bc1_fit; clamping can bend the line), pixels follow their selectors.  For an
 // ETC1S source the brightest used colour is >= the darkest in every channel, so colour0 >= colour1 and the swap never runs (all 32^3 x 8
-// endpoints x 10 selector ranges enumerated: tests/test_hipemu_transcode_ref.py); equal endpoints happen (a block of one selector).  BC3 = a BC4
-// alpha block (alpha0 = highest, alpha1 = lowest level the block uses, eight-value mode, every level on its nearest palette value; equal
-// levels: index 0) followed by the same colour block, which BC3 always reads in four-colour mode.  Re-fits, not restatements of the basis
-// transcoder's tables (not in the reference): gated by PSNR against the RGBA32 decode through an independent decoder (tests/helpers.py)
-// and checked block by block against the plain reference of this rule in tests/transcode_ref.py (palette entries ascending, first best).
-// Layouts: colour0, colour1 (u16 LE, R in the top 5 bits), 16 x 2-bit indices raster order from bit 0; alpha0, alpha1, 16 x 3-bit indices.
+// endpoints x 10 selector ranges enumerated: tests/test_hipemu_transcode_ref.py); equal endpoints happen (a block of one selector).  BC3 = a
+// BC4 block of the alpha slice's four levels (bc4_fit, endpoints from the levels the block uses), then the same colour block.  Re-fits, not
+// restatements of the basis transcoder's tables (not in the reference): gated by PSNR against the RGBA32 decode through an independent
+// decoder (tests/helpers.py) and checked block by block against the plain reference of this rule in tests/transcode_ref.py.
 template <bool BC3>
 __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc13(TexDecJob *jobs) {
-  TexDecJob &J = jobs[blockIdx.z];
-  if (J.status != 0) return;
-  const uint32_t layer = blockIdx.y, b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
-  if (layer >= J.layers || b >= J.bx * J.by) return;
-  const size_t nbk = (size_t)J.bx * J.by, o = (size_t)(layer << J.ashift) * nbk + b;
-  const int MODS[8][4] = { { -8, -2, 2, 8 }, { -17, -5, 5, 17 }, { -29, -9, 9, 29 }, { -42, -13, 13, 42 }, { -60, -18, 18, 60 }, { -80, -24, 24, 80 }, { -106, -33, 33, 106 }, { -183, -47, 47, 183 } };
+  const TexDecJob &J = jobs[blockIdx.z];
+  uint32_t layer, b; size_t o; if (!tdec_begin(J, layer, b, o)) return;
   uint8_t *out = J.out[layer] + (BC3 ? 16 : 8) * (size_t)b;
   if (BC3) {
-    int al[4] = { 255, 255, 255, 255 }; uint32_t asel = 0;
-    if (J.ashift) {
-      const uint8_t *ae = J.endpoints + 4 * (size_t)J.ei[o + nbk]; asel = J.selectors[J.si[o + nbk]];
-      for (int k = 0; k < 4; k++) { const int v = ((ae[1] << 3) | (ae[1] >> 2)) + MODS[ae[3] & 7][k]; al[k] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-    }
-    uint32_t used = J.ashift ? 0u : 1u;
-    if (J.ashift) for (int i = 0; i < 16; i++) used |= 1u << ((asel >> (2 * i)) & 3u);
-    int a0 = 0, a1 = 255;
-    for (int k = 0; k < 4; k++) if ((used >> k) & 1u) { a0 = al[k] > a0 ? al[k] : a0; a1 = al[k] < a1 ? al[k] : a1; }
-    uint32_t lvl[4] = { 0, 0, 0, 0 };
-    if (a0 > a1) {
-      for (int k = 0; k < 4; k++) {
-        int be = 1 << 30;
-        for (int j = 0; j < 8; j++) { const int v = j == 0 ? a0 : (j == 1 ? a1 : ((8 - j) * a0 + (j - 1) * a1) / 7); const int d = v - al[k]; if (d * d < be) { be = d * d; lvl[k] = (uint32_t)j; } }
-      }
-    }
-    unsigned long long bits = 0;
-    for (int i = 0; i < 16; i++) bits |= (unsigned long long)lvl[(asel >> (2 * i)) & 3u] << (3 * i);
-    out[0] = (uint8_t)a0; out[1] = (uint8_t)a1;
-    for (int k = 0; k < 6; k++) out[2 + k] = (uint8_t)(bits >> (8 * k));
+    int al[4] = { 255, 255, 255, 255 }; uint32_t asel = 0, used = 1u;      // an opaque file: level 255 everywhere
+    if (J.ashift) { tdec_levels(tdec_fetch_alpha(J, o, asel), al); used = tdec_used(asel); }
+    int a0, a1; uint32_t lvl[4]; bc4_fit<4>([&](int k) { return al[k]; }, used, a0, a1);
+    for (int k = 0; k < 4; k++) lvl[k] = bc4_nearest(a0, a1, al[k]);
+    bc4_pack(out, a0, a1, [&](int i) { return tdec_pick(lvl, asel, i); });
     out += 8;
   }
-  const uint8_t *e = J.endpoints + 4 * (size_t)J.ei[o]; const uint32_t sel = J.selectors[J.si[o]];
-  int col[4][3];
-  for (int c = 0; c < 3; c++) {
-    const int base = (e[c] << 3) | (e[c] >> 2);
-    for (int k = 0; k < 4; k++) { const int v = base + MODS[e[3] & 7][k]; col[k][c] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-  }
-  // endpoints: brightest colour the block uses -> colour0, darkest -> colour1, rounded to 5 / 6 / 5 bits
-  uint32_t cused = 0; for (int i = 0; i < 16; i++) cused |= 1u << ((sel >> (2 * i)) & 3u);
-  int klo = 0, khi = 3;
-  while (!((cused >> klo) & 1u)) klo++;
-  while (!((cused >> khi) & 1u)) khi--;
-  const int q0[3] = { (col[khi][0] * 31 + 127) / 255, (col[khi][1] * 63 + 127) / 255, (col[khi][2] * 31 + 127) / 255 };
-  const int q1[3] = { (col[klo][0] * 31 + 127) / 255, (col[klo][1] * 63 + 127) / 255, (col[klo][2] * 31 + 127) / 255 };
-  uint32_t c0 = (uint32_t)((q0[0] << 11) | (q0[1] << 5) | q0[2]), c1 = (uint32_t)((q1[0] << 11) | (q1[1] << 5) | q1[2]);
-  int pal[4][3];
-  { const int e0[3] = { (q0[0] << 3) | (q0[0] >> 2), (q0[1] << 2) | (q0[1] >> 4), (q0[2] << 3) | (q0[2] >> 2) };
-    const int e1[3] = { (q1[0] << 3) | (q1[0] >> 2), (q1[1] << 2) | (q1[1] >> 4), (q1[2] << 3) | (q1[2] >> 2) };
-    for (int c = 0; c < 3; c++) { pal[0][c] = e0[c]; pal[1][c] = e1[c]; pal[2][c] = (2 * e0[c] + e1[c]) / 3; pal[3][c] = (e0[c] + 2 * e1[c]) / 3; } }
-  uint32_t map[4] = { 0, 0, 0, 0 };
-  if (c0 != c1) {
-    for (int k = 0; k < 4; k++) {
-      int be = 1 << 30;
-      for (int j = 0; j < 4; j++) { int d = 0; for (int c = 0; c < 3; c++) { const int t = pal[j][c] - col[k][c]; d += t * t; } if (d < be) { be = d; map[k] = (uint32_t)j; } }
-    }
-    if (c0 < c1) {                                          // four-colour mode wants colour0 > colour1: swap, 0 <-> 1 and 2 <-> 3
-      const uint32_t t = c0; c0 = c1; c1 = t;
-      for (int k = 0; k < 4; k++) map[k] ^= 1u;
-    }
-  }
-  uint32_t idx = 0;
-  for (int i = 0; i < 16; i++) idx |= map[(sel >> (2 * i)) & 3u] << (2 * i);
-  out[0] = (uint8_t)c0; out[1] = (uint8_t)(c0 >> 8); out[2] = (uint8_t)c1; out[3] = (uint8_t)(c1 >> 8);
-  out[4] = (uint8_t)idx; out[5] = (uint8_t)(idx >> 8); out[6] = (uint8_t)(idx >> 16); out[7] = (uint8_t)(idx >> 24);
+  uint32_t sel, map[4]; int col[4][3], klo, khi;
+  tdec_colours(tdec_fetch(J, o, sel), col); tdec_used_range(sel, klo, khi);
+  Bc1Fit F; bc1_fit(col[khi], col[klo], F);
+  for (int k = 0; k < 4; k++) map[k] = bc1_nearest(F, col[k][0], col[k][1], col[k][2]);
+  bc1_pack(out, F.c0, F.c1, [&](int i) { return tdec_pick(map, sel, i); });
 }
 
 // ---- K3'': BC7 target (what KTX2Loader picks on desktop GPUs, reference src/lib/KTX2Loader.js:591-689: astc, then bptc).  An ETC1S
@@ -531,29 +440,16 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc13(TexDecJob *jobs) {
 // hence the search; indices ascending, the first best wins); the block keeps the mode with the smaller error summed over its 16
 // pixels (ties: mode 5).  Not a restatement of the basis transcoder's table-driven mode-5 path: the gate for this target is PSNR
 // against the RGBA32 decode, and every block is checked against the plain reference of this rule in tests/transcode_ref.py.
-// Bit layouts, LSB first.  Mode 5: 6 bits (1 << 5); rotation 2 (= 0); R0 R1 G0 G1 B0 B1, 7 bits each; A0 A1, 8 bits each;
-// colour indices 1 + 15 * 2 bits; alpha indices 1 + 15 * 2 bits (all 0).  Mode 6: 7 bits (1 << 6); R0 R1 G0 G1 B0 B1 A0 A1,
-// 7 bits each; P0 P1; indices 3 + 15 * 4 bits.  Pixel 0's index has its MSB implied 0: otherwise swap the endpoints and
-// complement the indices.  Pixels in raster order.
+// Bit layouts: tex_blocks.hpp.
 __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc7(TexDecJob *jobs) {
-  TexDecJob &J = jobs[blockIdx.z];
-  if (J.status != 0) return;
-  const uint32_t layer = blockIdx.y, b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
-  if (layer >= J.layers || b >= J.bx * J.by) return;
-  const size_t o = (size_t)(layer << J.ashift) * J.bx * J.by + b;
-  const uint8_t *e = J.endpoints + 4 * (size_t)J.ei[o]; const uint32_t sel = J.selectors[J.si[o]];
-  const int MODS[8][4] = { { -8, -2, 2, 8 }, { -17, -5, 5, 17 }, { -29, -9, 9, 29 }, { -42, -13, 13, 42 }, { -60, -18, 18, 60 }, { -80, -24, 24, 80 }, { -106, -33, 33, 106 }, { -183, -47, 47, 183 } };
-  const int W2[4] = { 0, 21, 43, 64 };
-  const int W4[16] = { 0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64 };
-  int col[4][3], lo7[3], hi7[3];
-  for (int c = 0; c < 3; c++) {
-    const int base = (e[c] << 3) | (e[c] >> 2);
-    for (int k = 0; k < 4; k++) { const int v = base + MODS[e[3] & 7][k]; col[k][c] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-  }
+  const TexDecJob &J = jobs[blockIdx.z];
+  uint32_t layer, b; size_t o; if (!tdec_begin(J, layer, b, o)) return;
+  uint32_t sel; int col[4][3], lo7[3], hi7[3];
+  tdec_colours(tdec_fetch(J, o, sel), col);
   uint32_t hist[4] = { 0, 0, 0, 0 };
   for (int i = 0; i < 16; i++) hist[(sel >> (2 * i)) & 3u]++;
   int klo = 0, khi = 3;                                  // the darkest / brightest colour the block USES (a solid block: one colour, equal endpoints)
-  while (!hist[klo]) klo++;
+  while (!hist[klo]) klo++;                              // (from the histogram the error sums need anyway, as before the block formats were shared)
   while (!hist[khi]) khi--;
   for (int c = 0; c < 3; c++) { lo7[c] = col[klo][c] >> 1; hi7[c] = col[khi][c] >> 1; }
   uint32_t idx5[4], idx6[4], err5 = 0, err6 = 0;
@@ -561,51 +457,44 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_tdec_bc7(TexDecJob *jobs) {
     uint32_t b5 = 0, e5 = 0xffffffffu, b6 = 0, e6 = 0xffffffffu;
     for (uint32_t w = 0; w < 4; w++) {
       uint32_t err = 0;
-      for (int c = 0; c < 3; c++) { const int l = (lo7[c] << 1) | (lo7[c] >> 6), h = (hi7[c] << 1) | (hi7[c] >> 6), d = ((l * (64 - W2[w]) + h * W2[w] + 32) >> 6) - col[k][c]; err += (uint32_t)(d * d); }
+      for (int c = 0; c < 3; c++) { const int d = bc7_interp((lo7[c] << 1) | (lo7[c] >> 6), (hi7[c] << 1) | (hi7[c] >> 6), bc7_w2(w)) - col[k][c]; err += (uint32_t)(d * d); }
       if (err < e5) { e5 = err; b5 = w; }
     }
     for (uint32_t w = 0; w < 16; w++) {
       uint32_t err = 0;
-      for (int c = 0; c < 3; c++) { const int d = (((2 * lo7[c] + 1) * (64 - W4[w]) + (2 * hi7[c] + 1) * W4[w] + 32) >> 6) - col[k][c]; err += (uint32_t)(d * d); }
+      for (int c = 0; c < 3; c++) { const int d = bc7_interp(2 * lo7[c] + 1, 2 * hi7[c] + 1, bc7_w4(w)) - col[k][c]; err += (uint32_t)(d * d); }
       if (err < e6) { e6 = err; b6 = w; }
     }
     idx5[k] = b5; idx6[k] = b6; err5 += hist[k] * e5; err6 += hist[k] * e6;
   }
-  unsigned long long lo, hi = 0; int pos;
-  auto put = [&](unsigned long long v, int n) { if (pos < 64) { lo |= v << pos; if (pos + n > 64) hi |= v >> (64 - pos); } else hi |= v << (pos - 64); pos += n; };
   // A file with alpha slices (what the stock loader asks BC7 with alpha for, src/lib/KTX2Loader.js:672-676): always mode 5, whose alpha has
-  // its own 8-bit endpoints and 2-bit indices.  The alpha block's four levels (green channel of the alpha slice, as the basis transcoder
-  // takes them) give the endpoints (lowest / highest level the block uses, exact) and every level the first nearest of the four interpolated values.
+  // its own 8-bit endpoints and 2-bit indices.  The alpha block's four levels give the endpoints (lowest / highest level the block uses,
+  // exact) and every level the first nearest of the four interpolated values.
   uint32_t aidx[4] = { 0, 0, 0, 0 }, asel = 0; int a_lo = 255, a_hi = 255;
   if (J.ashift) {
-    const size_t oa = o + (size_t)J.bx * J.by;
-    const uint8_t *ae = J.endpoints + 4 * (size_t)J.ei[oa]; asel = J.selectors[J.si[oa]];
-    int al[4];
-    for (int k = 0; k < 4; k++) { const int v = ((ae[1] << 3) | (ae[1] >> 2)) + MODS[ae[3] & 7][k]; al[k] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-    uint32_t aused = 0; for (int i = 0; i < 16; i++) aused |= 1u << ((asel >> (2 * i)) & 3u);
-    int alo = 0, ahi = 3;
-    while (!((aused >> alo) & 1u)) alo++;
-    while (!((aused >> ahi) & 1u)) ahi--;
+    int al[4], alo, ahi;
+    tdec_levels(tdec_fetch_alpha(J, o, asel), al); tdec_used_range(asel, alo, ahi);
     a_lo = al[alo]; a_hi = al[ahi];
-    for (int k = 0; k < 4; k++) { uint32_t bw = 0; int be = 1 << 30; for (uint32_t w = 0; w < 4; w++) { const int d = ((a_lo * (64 - W2[w]) + a_hi * W2[w] + 32) >> 6) - al[k]; if (d * d < be) { be = d * d; bw = w; } } aidx[k] = bw; }
+    for (int k = 0; k < 4; k++) { uint32_t bw = 0; int be = 1 << 30; for (uint32_t w = 0; w < 4; w++) { const int d = bc7_interp(a_lo, a_hi, bc7_w2(w)) - al[k]; if (d * d < be) { be = d * d; bw = w; } } aidx[k] = bw; }
   }
+  TBits128 B; B.lo = 0; B.hi = 0; int bo = 0;
   if (err5 <= err6 || J.ashift) {
     const bool swap = idx5[sel & 3u] >= 2u;              // pixel 0 = selector bits 0..1 (x = 0, y = 0)
     const bool aswap = aidx[asel & 3u] >= 2u;            // the alpha index set has its own anchor
-    lo = 1ull << 5; pos = 8;
-    for (int c = 0; c < 3; c++) { put((unsigned)(swap ? hi7[c] : lo7[c]), 7); put((unsigned)(swap ? lo7[c] : hi7[c]), 7); }
-    put((unsigned)(aswap ? a_hi : a_lo), 8); put((unsigned)(aswap ? a_lo : a_hi), 8);
-    for (int i = 0; i < 16; i++) { uint32_t ix = idx5[(sel >> (2 * i)) & 3u]; if (swap) ix = 3u - ix; put(ix, i == 0 ? 1 : 2); }
-    if (J.ashift) for (int i = 0; i < 16; i++) { uint32_t ix = aidx[(asel >> (2 * i)) & 3u]; if (aswap) ix = 3u - ix; put(ix, i == 0 ? 1 : 2); }
+    B.put_raw(bo, 1u << 5, 6); B.put_raw(bo, 0, 2);
+    for (int c = 0; c < 3; c++) { B.put_raw(bo, (uint32_t)(swap ? hi7[c] : lo7[c]), 7); B.put_raw(bo, (uint32_t)(swap ? lo7[c] : hi7[c]), 7); }
+    B.put_raw(bo, (uint32_t)(aswap ? a_hi : a_lo), 8); B.put_raw(bo, (uint32_t)(aswap ? a_lo : a_hi), 8);
+    for (int i = 0; i < 16; i++) { const uint32_t ix = tdec_pick(idx5, sel, i); B.put_raw(bo, swap ? 3u - ix : ix, i == 0 ? 1 : 2); }
+    if (J.ashift) for (int i = 0; i < 16; i++) { const uint32_t ix = tdec_pick(aidx, asel, i); B.put_raw(bo, aswap ? 3u - ix : ix, i == 0 ? 1 : 2); }
   } else {
     const bool swap = idx6[sel & 3u] >= 8u;
-    lo = 1ull << 6; pos = 7;
-    for (int c = 0; c < 3; c++) { put((unsigned)(swap ? hi7[c] : lo7[c]), 7); put((unsigned)(swap ? lo7[c] : hi7[c]), 7); }
-    put(127u, 7); put(127u, 7); put(1u, 1); put(1u, 1);
-    for (int i = 0; i < 16; i++) { uint32_t ix = idx6[(sel >> (2 * i)) & 3u]; if (swap) ix = 15u - ix; put(ix, i == 0 ? 3 : 4); }
+    B.put_raw(bo, 1u << 6, 7);
+    for (int c = 0; c < 3; c++) { B.put_raw(bo, (uint32_t)(swap ? hi7[c] : lo7[c]), 7); B.put_raw(bo, (uint32_t)(swap ? lo7[c] : hi7[c]), 7); }
+    B.put_raw(bo, 127u, 7); B.put_raw(bo, 127u, 7); B.put_raw(bo, 1u, 1); B.put_raw(bo, 1u, 1);
+    for (int i = 0; i < 16; i++) { const uint32_t ix = tdec_pick(idx6, sel, i); B.put_raw(bo, swap ? 15u - ix : ix, i == 0 ? 3 : 4); }
   }
   unsigned long long *out = (unsigned long long *)(J.out[layer] + 16 * (size_t)b);
-  out[0] = lo; out[1] = hi;
+  out[0] = B.lo; out[1] = B.hi;
 }
 
 // ================================================================================================

@@ -10,6 +10,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include "tex_blocks.hpp"               // t_clampi, t_expand5, t_inten: the ETC1 basics
 
 #define TEX_MAX_LAYERS 64
 #define TEX_MAX_CODEBOOK 16128
@@ -58,15 +59,6 @@ struct TexJob {
   unsigned long long slice_bits[TEX_MAX_LAYERS];
   uint32_t n_skipped;
 };
-
-__device__ __forceinline__ int t_clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__device__ __forceinline__ int t_expand5(int c) { return (c << 3) | (c >> 2); }
-__device__ __forceinline__ int t_inten(int t, int s) {
-  // g_etc1_inten_tables, linear selector order low -> high
-  const int hi_[8] = { 8, 17, 29, 42, 60, 80, 106, 183 }, lo_[8] = { 2, 5, 9, 13, 18, 24, 33, 47 };
-  const int m = (s == 0 || s == 3) ? hi_[t] : lo_[t];
-  return s < 2 ? -m : m;
-}
 
 // 4x4 block fetch with y-flip and edge replication; px[i] = R | G<<8 | B<<16 (i = y*4+x)
 // amask (optional): AND of the texels' alpha bytes (bits 24..31), for the opacity check of the ETC1S path

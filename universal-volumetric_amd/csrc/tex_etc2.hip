@@ -20,6 +20,7 @@
 // bytes (profiles/r14_etc2_direct.json); the one-lane form was dropped.
 // A fit travels as one 64-bit word: error << 32 | table << 15 | r << 10 | g << 5 | b (errors are at most 16 x 3 x 255^2 < 2^22).
 // Every read is bounded by W and H (clamped coordinates), every write by the block count of the layer.
+// The ETC1 tables, expansions, pixel-index order, planes and the block's byte layout are those of tex_blocks.hpp.
 #include "uvol_common.hpp"
 #include "tex_device.hpp"
 
@@ -30,9 +31,7 @@
 #define E2_MAX_GRID 32768u                               /* workgroups; the kernel strides beyond (2 097 152 blocks per round) */
 #endif
 
-__device__ __forceinline__ int e2_mag_s(int t) { return (int)((0x2F2118120D090502ull >> (8 * t)) & 255u); }      // 2, 5, 9, 13, 18, 24, 33, 47
-__device__ __forceinline__ int e2_mag_l(int t) { return (int)((0xB76A503C2A1D1108ull >> (8 * t)) & 255u); }      // 8, 17, 29, 42, 60, 80, 106, 183
-template <int TOP> __device__ __forceinline__ int e2_expand(int b) { return TOP == 31 ? ((b << 3) | (b >> 2)) : b * 17; }
+template <int TOP> __device__ __forceinline__ int e2_expand(int b) { return TOP == 31 ? t_expand5(b) : t_expand4(b); }
 __device__ __forceinline__ uint32_t e2_err(unsigned long long w) { return (uint32_t)(w >> 32); }
 __device__ __forceinline__ unsigned long long e2_word(uint32_t err, uint32_t code) { return ((unsigned long long)err << 32) | code; }
 
@@ -71,7 +70,7 @@ __device__ __forceinline__ void e2_means(const uint32_t h[8], int q5[3], int q4[
 
 // E(base, t): sum over the half's texels of the smallest squared error among the four modified colours (each channel clamped to 0 .. 255)
 __device__ inline uint32_t e2_half_err(const uint32_t h[8], int br, int bg, int bb, int t) {
-  const int S = e2_mag_s(t), L = e2_mag_l(t);
+  const int S = etc1_mag_s(t), L = etc1_mag_l(t);
   const int lo = br < bg ? (br < bb ? br : bb) : (bg < bb ? bg : bb), hi = br > bg ? (br > bb ? br : bb) : (bg > bb ? bg : bb);
   uint32_t tot = 0;
   if (lo - L >= 0 && hi + L <= 255) {
@@ -90,8 +89,8 @@ __device__ inline uint32_t e2_half_err(const uint32_t h[8], int br, int bg, int 
   for (int j = 0; j < 8; j++) {
     const int r = (int)(h[j] & 255u), g = (int)((h[j] >> 8) & 255u), b = (int)((h[j] >> 16) & 255u);
     uint32_t be = 0xffffffffu;
-    for (int s = 0; s < 4; s++) {
-      const int m = (s & 1) ? L : S, d = (s & 2) ? -m : m;
+    for (uint32_t s = 0; s < 4; s++) {
+      const int d = etc1_mod(S, L, s);
       const int dr = t_clampi(br + d, 0, 255) - r, dg = t_clampi(bg + d, 0, 255) - g, db = t_clampi(bb + d, 0, 255) - b;
       const uint32_t e = (uint32_t)(dr * dr + dg * dg + db * db);
       if (e < be) be = e;
@@ -156,7 +155,7 @@ __device__ inline unsigned long long e2_flip_pick(const unsigned long long r5[2]
   return e2_word(e_ind, hdr);
 }
 // pixel indices of rows [y0, y1) under the block header `hdr` (bytes 0 .. 3, read back as a decoder reads them): every texel takes the first
-// nearest of the four modified colours in the order 0 .. 3 = +small, +large, -small, -large; bit 4 x + y of the msb / lsb planes
+// nearest of the four modified colours in pixel-index order; -> msb plane | lsb plane << 16
 __device__ inline uint32_t e2_select(const uint32_t px[16], uint32_t hdr, int y0, int y1) {
   const uint32_t b3 = hdr >> 24; const bool diff = (b3 & 2u) != 0; const int flip = (int)(b3 & 1u);
   int base[2][3];
@@ -169,17 +168,16 @@ __device__ inline uint32_t e2_select(const uint32_t px[16], uint32_t hdr, int y0
   const int tab[2] = { (int)(b3 >> 5), (int)((b3 >> 2) & 7u) };
   uint32_t msb = 0, lsb = 0;
   for (int y = y0; y < y1; y++) for (int x = 0; x < 4; x++) {
-    const int hf = flip ? (y >= 2) : (x >= 2), S = e2_mag_s(tab[hf]), L = e2_mag_l(tab[hf]);
+    const int hf = flip ? (y >= 2) : (x >= 2), S = etc1_mag_s(tab[hf]), L = etc1_mag_l(tab[hf]);
     const uint32_t p = px[4 * y + x]; const int r = (int)(p & 255u), g = (int)((p >> 8) & 255u), b = (int)((p >> 16) & 255u);
     uint32_t be = 0xffffffffu, bi = 0;
     for (uint32_t s = 0; s < 4; s++) {
-      const int m = (s & 1u) ? L : S, d = (s & 2u) ? -m : m;
+      const int d = etc1_mod(S, L, s);
       const int dr = t_clampi(base[hf][0] + d, 0, 255) - r, dg = t_clampi(base[hf][1] + d, 0, 255) - g, db = t_clampi(base[hf][2] + d, 0, 255) - b;
       const uint32_t e = (uint32_t)(dr * dr + dg * dg + db * db);
       if (e < be) { be = e; bi = s; }
     }
-    const int i = 4 * x + y;
-    msb |= (bi >> 1) << i; lsb |= (bi & 1u) << i;
+    etc1_plane_put(msb, lsb, x, y, bi);
   }
   return msb | (lsb << 16);
 }
@@ -207,10 +205,7 @@ __global__ void __launch_bounds__(E2_BLOCK) k_etc2_encode(const uint8_t *const *
     const uint32_t hdr = (uint32_t)(e2_err(pick1) < e2_err(pick0) ? pick1 : pick0);
     uint32_t sel = e2_select(px, hdr, k, k + 1);
     sel |= __shfl_xor(sel, 1); sel |= __shfl_xor(sel, 2);
-    if (k == 0 && live) {
-      const uint32_t msb = sel & 0xffffu, lsb = sel >> 16;
-      *reinterpret_cast<uint2 *>(outs[li] + 8 * (size_t)b) = make_uint2(hdr, (msb >> 8) | ((msb & 255u) << 8) | ((lsb >> 8) << 16) | ((lsb & 255u) << 24));
-    }
+    if (k == 0 && live) *reinterpret_cast<uint2 *>(outs[li] + 8 * (size_t)b) = etc1_words(hdr, sel & 0xffffu, sel >> 16);      // blocks[] are 8-byte aligned: one store
   }
 }
 

@@ -10,8 +10,10 @@
 //
 // One thread per 4x4 block, blocks are independent: a streaming kernel (64 B of texels in, 16 B out per block) whose
 // arithmetic is a handful of exact integer least-squares fits per block.  Everything is integer and deterministic (the tests compare
-// every output byte with the CPU restatement of the same algorithm).  No MFMA: there is no contraction; the bound is VALU integer throughput and, for the transcodes, HBM.
+// every output byte with the CPU restatement of the same algorithm).  The ETC1 / EAC / BC1 / BC4 / BC7 rules the hints and the transcode
+// targets need are those of tex_blocks.hpp.  No MFMA: there is no contraction; the bound is VALU integer throughput and, for the transcodes, HBM.
 #include "uvol_common.hpp"
+#include "tex_blocks.hpp"
 #include <dlfcn.h>
 #include <algorithm>
 
@@ -82,15 +84,8 @@ __device__ __forceinline__ long long u_udiv_exact(long long nn, long long d) {  
 __device__ __forceinline__ long long u_rdiv(long long n, long long d) { return n >= 0 ? u_udiv_exact(n + d / 2, d) : -u_udiv_exact(-n + d / 2, d); }
 __device__ __forceinline__ int u_comp(uint32_t px, int c) { return (int)((px >> (8 * c)) & 255u); }
 
-// 128-bit block under construction (LSB first)
-struct UBits {
-  unsigned long long lo, hi;
-  __device__ __forceinline__ void put(int &o, uint32_t v, int n) {
-    if (n <= 0) return;
-    const unsigned long long x = (unsigned long long)v & ((1ull << n) - 1ull);
-    if (o < 64) { lo |= x << o; if (o + n > 64) hi |= x >> (64 - o); } else hi |= x << (o - 64);
-    o += n;
-  }
+// 128-bit block under construction (the writer: tex_blocks.hpp) and read back
+struct UBits : TBits128 {
   __device__ __forceinline__ uint32_t get(int &o, int n) const {
     if (n <= 0) return 0;
     unsigned long long x;
@@ -197,13 +192,12 @@ __device__ inline void u_encode_block(const uint32_t px[16], const UTab *T, UBit
   B.lo = 0; B.hi = 0; int o = 0;
   bool same = true, alpha = false;
   for (int i = 0; i < 16; i++) { same &= px[i] == px[0]; alpha |= (px[i] >> 24) != 255u; }
-  const int lo_[8] = { 2, 5, 9, 13, 18, 24, 33, 47 }, hi_[8] = { 8, 17, 29, 42, 60, 80, 106, 183 };
   if (same) {                                                           // mode 8: the colour + the ETC1 hint (table, selector, 5-bit base) closest to it
     uint32_t be = 0xffffffffu; int bt = 0, bsel = 0, b5[3] = { 0, 0, 0 };
     for (int t = 0; t < 8; t++) for (int sl = 0; sl < 4; sl++) {
-      const int mod = sl == 0 ? -hi_[t] : (sl == 1 ? -lo_[t] : (sl == 2 ? lo_[t] : hi_[t]));
+      const int mod = t_inten(t, sl);
       uint32_t e = 0; int cb[3];
-      for (int c = 0; c < 3; c++) { uint32_t bc = 0xffffffffu; int bb = 0; for (int q = 0; q < 32; q++) { int v = ((q << 3) | (q >> 2)) + mod; v = v < 0 ? 0 : (v > 255 ? 255 : v); const int dd = v - u_comp(px[0], c); if ((uint32_t)(dd * dd) < bc) { bc = (uint32_t)(dd * dd); bb = q; } } e += bc; cb[c] = bb; }
+      for (int c = 0; c < 3; c++) { uint32_t bc = 0xffffffffu; int bb = 0; for (int q = 0; q < 32; q++) { const int dd = t_clampi(t_expand5(q) + mod, 0, 255) - u_comp(px[0], c); if ((uint32_t)(dd * dd) < bc) { bc = (uint32_t)(dd * dd); bb = q; } } e += bc; cb[c] = bb; }
       if (e < be) { be = e; bt = t; bsel = sl; b5[0] = cb[0]; b5[1] = cb[1]; b5[2] = cb[2]; }
     }
     B.put(o, 0x17, 5);
@@ -258,13 +252,13 @@ __device__ inline void u_encode_block(const uint32_t px[16], const UTab *T, UBit
   int inten[2] = { 0, 0 };
   for (int h = 0; h < 2; h++) {
     const int x0 = 2 * h; int base[3];
-    for (int c = 0; c < 3; c++) { int sm = 0; for (int y = 0; y < 4; y++) for (int x = x0; x < x0 + 2; x++) sm += u_comp(dec[4 * y + x], c); const int avg = (sm + 4) / 8; base[c] = ((avg * 15 + 127) / 255) * 17; }
+    for (int c = 0; c < 3; c++) { int sm = 0; for (int y = 0; y < 4; y++) for (int x = x0; x < x0 + 2; x++) sm += u_comp(dec[4 * y + x], c); const int avg = (sm + 4) / 8; base[c] = t_expand4((avg * 15 + 127) / 255); }
     uint32_t be = 0xffffffffu;
     for (int t = 0; t < 8; t++) {
-      uint32_t e = 0; const int mod[4] = { -hi_[t], -lo_[t], lo_[t], hi_[t] };
+      uint32_t e = 0;
       for (int y = 0; y < 4; y++) for (int x = x0; x < x0 + 2; x++) {
         uint32_t bs = 0xffffffffu;
-        for (int sl = 0; sl < 4; sl++) { uint32_t es = 0; for (int c = 0; c < 3; c++) { int v = base[c] + mod[sl]; v = v < 0 ? 0 : (v > 255 ? 255 : v); const int dd = v - u_comp(dec[4 * y + x], c); es += (uint32_t)(dd * dd); } bs = es < bs ? es : bs; }
+        for (int sl = 0; sl < 4; sl++) { uint32_t es = 0; for (int c = 0; c < 3; c++) { const int dd = t_clampi(base[c] + t_inten(t, sl), 0, 255) - u_comp(dec[4 * y + x], c); es += (uint32_t)(dd * dd); } bs = es < bs ? es : bs; }
         e += bs;
       }
       if (e < be) { be = e; inten[h] = t; }
@@ -406,12 +400,8 @@ __device__ inline int u_to_astc(const UBits &B, const UConst *K, UBits &A) {
 //    takes the p-bit under which its four 8-bit values are represented best, every texel the index of the nearest interpolated colour;
 //  * dual-plane modes (6, 11) -> BC7 mode 5 (RGB 7-bit endpoints / 2-bit indices + a separate 8-bit scalar channel with its own indices;
 //    the rotation puts the block's second-plane channel there): UASTC's and BC7's 2-bit weights are the same {0, 21, 43, 64}.
-// Bit layouts as in tex_decode.hip (k_tdec_bc7), LSB first.
-struct UBc7 { unsigned long long lo, hi; int pos;
-  __device__ __forceinline__ void put(unsigned long long v, int n) { if (pos < 64) { lo |= v << pos; if (pos + n > 64) hi |= v >> (64 - pos); } else hi |= v << (pos - 64); pos += n; } };
-__device__ inline void u_to_bc7(const ULog &L, uint32_t solid, const uint32_t px[16], const UTab *T, UBits &out) {
-  const int W2[4] = { 0, 21, 43, 64 };
-  const int W4[16] = { 0, 4, 9, 13, 17, 21, 26, 30, 34, 38, 43, 47, 51, 55, 60, 64 };
+// Bit layouts, weights and the writer: tex_blocks.hpp.
+__device__ inline void u_to_bc7(const ULog &L, uint32_t solid, const uint32_t px[16], const UTab *T, UBits &B) {
   int lo[4] = { 0, 0, 0, 255 }, hi[4] = { 0, 0, 0, 255 }, dual = 0, ccs = 0;
   if (L.mode == 8) { for (int c = 0; c < 4; c++) lo[c] = hi[c] = (int)((solid >> (8 * c)) & 255u); }
   else {
@@ -419,7 +409,7 @@ __device__ inline void u_to_bc7(const ULog &L, uint32_t solid, const uint32_t px
     for (int c = 0; c < M.comps; c++) { lo[c] = T->uq[slot][L.ep[2 * c]]; hi[c] = T->uq[slot][L.ep[2 * c + 1]]; }
     dual = M.planes == 2; ccs = L.ccs;
   }
-  UBc7 B; B.lo = 0; B.hi = 0; B.pos = 0;
+  B.lo = 0; B.hi = 0; int o = 0;
   if (!dual) {
     int e7[2][4], pb[2] = { 0, 0 };
     for (int s = 0; s < 2; s++) {
@@ -435,16 +425,16 @@ __device__ inline void u_to_bc7(const ULog &L, uint32_t solid, const uint32_t px
       uint32_t bw = 0; int be = 1 << 30;
       for (int k = 0; k < 16; k++) {
         int err = 0;
-        for (int c = 0; c < 4; c++) { const int a = (e7[0][c] << 1) | pb[0], b = (e7[1][c] << 1) | pb[1], d = ((a * (64 - W4[k]) + b * W4[k] + 32) >> 6) - (int)((px[i] >> (8 * c)) & 255u); err += d * d; }
+        for (int c = 0; c < 4; c++) { const int d = bc7_interp((e7[0][c] << 1) | pb[0], (e7[1][c] << 1) | pb[1], bc7_w4(k)) - u_comp(px[i], c); err += d * d; }
         if (err < be) { be = err; bw = (uint32_t)k; }
       }
       idx[i] = bw;
     }
     const int swap = idx[0] >= 8u ? 1 : 0;
-    B.lo = 1ull << 6; B.pos = 7;
-    for (int c = 0; c < 4; c++) { B.put((unsigned)e7[swap][c], 7); B.put((unsigned)e7[swap ^ 1][c], 7); }
-    B.put((unsigned)pb[swap], 1); B.put((unsigned)pb[swap ^ 1], 1);
-    for (int i = 0; i < 16; i++) B.put(swap ? 15u - idx[i] : idx[i], i == 0 ? 3 : 4);
+    B.put_raw(o, 1u << 6, 7);
+    for (int c = 0; c < 4; c++) { B.put_raw(o, (uint32_t)e7[swap][c], 7); B.put_raw(o, (uint32_t)e7[swap ^ 1][c], 7); }
+    B.put_raw(o, (uint32_t)pb[swap], 1); B.put_raw(o, (uint32_t)pb[swap ^ 1], 1);
+    for (int i = 0; i < 16; i++) B.put_raw(o, swap ? 15u - idx[i] : idx[i], i == 0 ? 3 : 4);
   } else {
     const int rot = ccs == 3 ? 0 : ccs + 1;
     int src[3]; for (int k = 0; k < 3; k++) src[k] = (ccs < 3 && k == ccs) ? 3 : k;       // encoded colour channel k holds this actual channel
@@ -460,22 +450,20 @@ __device__ inline void u_to_bc7(const ULog &L, uint32_t solid, const uint32_t px
       uint32_t bw = 0; int be = 1 << 30;
       for (int k = 0; k < 4; k++) {
         int err = 0;
-        for (int c = 0; c < 3; c++) { const int a = (e7[0][c] << 1) | (e7[0][c] >> 6), b = (e7[1][c] << 1) | (e7[1][c] >> 6), d = ((a * (64 - W2[k]) + b * W2[k] + 32) >> 6) - (int)((px[i] >> (8 * src[c])) & 255u); err += d * d; }
+        for (int c = 0; c < 3; c++) { const int d = bc7_interp((e7[0][c] << 1) | (e7[0][c] >> 6), (e7[1][c] << 1) | (e7[1][c] >> 6), bc7_w2(k)) - u_comp(px[i], src[c]); err += d * d; }
         if (err < be) { be = err; bw = (uint32_t)k; }
       }
       ci[i] = bw; bw = 0; be = 1 << 30;
-      for (int k = 0; k < 4; k++) { const int d = ((a0 * (64 - W2[k]) + a1 * W2[k] + 32) >> 6) - (int)((px[i] >> (8 * ccs)) & 255u); if (d * d < be) { be = d * d; bw = (uint32_t)k; } }
+      for (int k = 0; k < 4; k++) { const int d = bc7_interp(a0, a1, bc7_w2(k)) - u_comp(px[i], ccs); if (d * d < be) { be = d * d; bw = (uint32_t)k; } }
       ai[i] = bw;
     }
     const int cswap = ci[0] >= 2u ? 1 : 0, aswap = ai[0] >= 2u ? 1 : 0;
-    B.lo = 1ull << 5; B.pos = 6;
-    B.put((unsigned)rot, 2);
-    for (int c = 0; c < 3; c++) { B.put((unsigned)e7[cswap][c], 7); B.put((unsigned)e7[cswap ^ 1][c], 7); }
-    B.put((unsigned)(aswap ? a1 : a0), 8); B.put((unsigned)(aswap ? a0 : a1), 8);
-    for (int i = 0; i < 16; i++) B.put(cswap ? 3u - ci[i] : ci[i], i == 0 ? 1 : 2);
-    for (int i = 0; i < 16; i++) B.put(aswap ? 3u - ai[i] : ai[i], i == 0 ? 1 : 2);
+    B.put_raw(o, 1u << 5, 6); B.put_raw(o, (uint32_t)rot, 2);
+    for (int c = 0; c < 3; c++) { B.put_raw(o, (uint32_t)e7[cswap][c], 7); B.put_raw(o, (uint32_t)e7[cswap ^ 1][c], 7); }
+    B.put_raw(o, (uint32_t)(aswap ? a1 : a0), 8); B.put_raw(o, (uint32_t)(aswap ? a0 : a1), 8);
+    for (int i = 0; i < 16; i++) B.put_raw(o, cswap ? 3u - ci[i] : ci[i], i == 0 ? 1 : 2);
+    for (int i = 0; i < 16; i++) B.put_raw(o, aswap ? 3u - ai[i] : ai[i], i == 0 ? 1 : 2);
   }
-  out.lo = B.lo; out.hi = B.hi;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -513,12 +501,6 @@ __global__ void __launch_bounds__(UVOL_BLOCK) UVOL_WAVES_PER_EU(4) k_uastc_encod
   dst[0] = B.lo; dst[1] = B.hi;
 }
 // target 0: RGBA8 (W x H x 4 per layer, stored row order), 1: ASTC 4x4 blocks, 2: BC7 blocks
-// EAC alpha modifier tables (ETC2 RGBA8's alpha half; the same values as tex_decode.hip's EAC_MOD)
-__device__ const int8_t UASTC_EAC_MOD[16][8] = {
-  { -3, -6, -9, -15, 2, 5, 8, 14 }, { -3, -7, -10, -13, 2, 6, 9, 12 }, { -2, -5, -8, -13, 1, 4, 7, 12 }, { -2, -4, -6, -13, 1, 3, 5, 12 },
-  { -3, -6, -8, -12, 2, 5, 7, 11 }, { -3, -7, -9, -11, 2, 6, 8, 10 }, { -4, -7, -8, -11, 3, 6, 7, 10 }, { -3, -5, -8, -11, 2, 4, 7, 10 },
-  { -2, -6, -8, -10, 1, 5, 7, 9 }, { -2, -5, -8, -10, 1, 4, 7, 9 }, { -2, -4, -8, -10, 1, 3, 7, 9 }, { -2, -5, -7, -10, 1, 4, 6, 9 },
-  { -3, -4, -7, -10, 2, 3, 6, 9 }, { -1, -2, -3, -10, 0, 1, 2, 9 }, { -4, -6, -8, -9, 3, 5, 7, 8 }, { -3, -5, -7, -9, 2, 4, 6, 8 } };
 __global__ void __launch_bounds__(UVOL_BLOCK) k_uastc_decode(UastcJob *jobs, const UConst *K, int target) {
   UastcJob &J = jobs[blockIdx.z];
   const uint32_t l = blockIdx.y, b = blockIdx.x * UVOL_BLOCK + threadIdx.x;
@@ -548,129 +530,82 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_uastc_decode(UastcJob *jobs, con
     // when both deltas fit, else in individual mode (4 bits each); per half-block the intensity table with the smallest error under per-texel
     // optimal modifiers; the flip with the smaller total error wins (ties: flip 0; tables and modifiers ascending, first best).  Gated by PSNR against the RGBA32
     // decode and checked block by block against the plain reference of this rule in tests/transcode_ref.py.
-    const int MAG[8][2] = { { 2, 8 }, { 5, 17 }, { 9, 29 }, { 13, 42 }, { 18, 60 }, { 24, 80 }, { 33, 106 }, { 47, 183 } };
     uint8_t *out = J.out[l] + (target == 6 ? 16 : 8) * (size_t)b;
     if (target == 6) {
-      int a0 = 0, a1 = 255;
-      for (int i = 0; i < 16; i++) { const int a = (int)(px[i] >> 24); a0 = a > a0 ? a : a0; a1 = a < a1 ? a : a1; }
-      int bt = 13, bm = 1, bb = a0;                       // constant alpha: table 13 has a zero modifier (index 4)
-      if (a0 > a1) {
-        const int mid = (a0 + a1 + 1) >> 1; uint32_t best = 0xffffffffu;
-        for (int t = 0; t < 16 && best; t++) for (int m = 1; m < 16 && best; m++) for (int db = -2; db <= 2; db++) {
-          const int base = mid + db; if (base < 0 || base > 255) continue;
-          int lv[8]; for (int j = 0; j < 8; j++) { const int v = base + m * UASTC_EAC_MOD[t][j]; lv[j] = v < 0 ? 0 : (v > 255 ? 255 : v); }
-          uint32_t err = 0;
-          for (int i = 0; i < 16 && err < best; i++) { const int a = (int)(px[i] >> 24); int be = 1 << 30; for (int j = 0; j < 8; j++) { const int d = lv[j] - a; be = d * d < be ? d * d : be; } err += (uint32_t)be; }
-          if (err < best) { best = err; bt = t; bm = m; bb = base; }
-        }
-      }
-      unsigned long long bits = 0;
-      for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) {
-        const int a = (int)(px[4 * y + x] >> 24); int be = 1 << 30; uint32_t bj = 0;
-        for (int j = 0; j < 8; j++) { int v = bb + bm * UASTC_EAC_MOD[bt][j]; v = v < 0 ? 0 : (v > 255 ? 255 : v); const int d = v - a; if (d * d < be) { be = d * d; bj = (uint32_t)j; } }
-        bits |= (unsigned long long)bj << (45 - 3 * (4 * x + y));
-      }
-      out[0] = (uint8_t)bb; out[1] = (uint8_t)((bm << 4) | bt);
-      for (int k = 0; k < 6; k++) out[2 + k] = (uint8_t)(bits >> (40 - 8 * k));
+      const auto alpha = [&](int i) { return (int)(px[i] >> 24); };
+      int bb, bm, bt; eac_fit<16>(alpha, [](int) { return 1u; }, true, bb, bm, bt);      // constant alpha takes the shortcut (the ETC1S path always searches)
+      eac_pack(out, bb, bm, bt, [&](int i) { return eac_nearest(bb, bm, bt, alpha(i)); });
       out += 8;
     }
-    uint32_t best_err = 0xffffffffu; uint8_t best_blk[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    uint32_t best_err = 0xffffffffu; uint2 best_blk = make_uint2(0u, 0u);
+#pragma unroll                                           /* both flips and both halves specialised: the half tests then fold to constants */
     for (int flip = 0; flip < 2; flip++) {
       int sum[2][3] = { { 0, 0, 0 }, { 0, 0, 0 } };
-      for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) { const int h = flip ? (y >= 2) : (x >= 2); for (int c = 0; c < 3; c++) sum[h][c] += (int)((px[4 * y + x] >> (8 * c)) & 255u); }
+      for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) { const int h = flip ? (y >= 2) : (x >= 2); for (int c = 0; c < 3; c++) sum[h][c] += u_comp(px[4 * y + x], c); }
       int q5[2][3], q4[2][3]; bool diff = true;
       for (int h = 0; h < 2; h++) for (int c = 0; c < 3; c++) { const int m8 = (sum[h][c] + 4) >> 3; q5[h][c] = (m8 * 31 + 127) / 255; q4[h][c] = (m8 * 15 + 127) / 255; }
       for (int c = 0; c < 3; c++) { const int d = q5[1][c] - q5[0][c]; if (d < -4 || d > 3) diff = false; }
       int base[2][3];
-      for (int h = 0; h < 2; h++) for (int c = 0; c < 3; c++) base[h][c] = diff ? ((q5[h][c] << 3) | (q5[h][c] >> 2)) : q4[h][c] * 17;
+      for (int h = 0; h < 2; h++) for (int c = 0; c < 3; c++) base[h][c] = diff ? t_expand5(q5[h][c]) : t_expand4(q4[h][c]);
       uint32_t err = 0; int tab[2] = { 0, 0 }; uint32_t msb = 0, lsb = 0;
+#pragma unroll
       for (int h = 0; h < 2; h++) {
         uint32_t bh = 0xffffffffu; uint32_t bm_ = 0, bl_ = 0;
         for (int t = 0; t < 8; t++) {
-          uint32_t e = 0, m_ = 0, l_ = 0;
+          uint32_t e = 0, m_ = 0, l_ = 0; const int S = etc1_mag_s(t), L = etc1_mag_l(t);
           for (int y = 0; y < 4; y++) for (int x = 0; x < 4; x++) {
             if ((flip ? (y >= 2) : (x >= 2)) != (h != 0)) continue;
             const uint32_t p = px[4 * y + x]; int be = 1 << 30; uint32_t bi = 0;
             for (uint32_t idx = 0; idx < 4; idx++) {
-              const int mod = (idx & 2u) ? -MAG[t][idx & 1u] : MAG[t][idx & 1u]; int d = 0;
-              for (int c = 0; c < 3; c++) { int v = base[h][c] + mod; v = v < 0 ? 0 : (v > 255 ? 255 : v); const int q = v - (int)((p >> (8 * c)) & 255u); d += q * q; }
+              const int mod = etc1_mod(S, L, idx); int d = 0;
+              for (int c = 0; c < 3; c++) { const int q = t_clampi(base[h][c] + mod, 0, 255) - u_comp(p, c); d += q * q; }
               if (d < be) { be = d; bi = idx; }
             }
-            e += (uint32_t)be; const int i = 4 * x + y; m_ |= (bi >> 1) << i; l_ |= (bi & 1u) << i;
+            e += (uint32_t)be; etc1_plane_put(m_, l_, x, y, bi);
           }
           if (e < bh) { bh = e; tab[h] = t; bm_ = m_; bl_ = l_; }
         }
         err += bh; msb |= bm_; lsb |= bl_;
       }
       if (err < best_err) {
-        best_err = err;
-        for (int c = 0; c < 3; c++) best_blk[c] = diff ? (uint8_t)((q5[0][c] << 3) | ((q5[1][c] - q5[0][c]) & 7)) : (uint8_t)((q4[0][c] << 4) | q4[1][c]);
-        best_blk[3] = (uint8_t)((tab[0] << 5) | (tab[1] << 2) | (diff ? 2 : 0) | flip);
-        best_blk[4] = (uint8_t)(msb >> 8); best_blk[5] = (uint8_t)msb; best_blk[6] = (uint8_t)(lsb >> 8); best_blk[7] = (uint8_t)lsb;
+        best_err = err; uint32_t cb[3];
+        for (int c = 0; c < 3; c++) cb[c] = (uint32_t)(diff ? (q5[0][c] << 3) | ((q5[1][c] - q5[0][c]) & 7) : (q4[0][c] << 4) | q4[1][c]);
+        best_blk = etc1_words(etc1_header(cb[0], cb[1], cb[2], (uint32_t)((tab[0] << 5) | (tab[1] << 2) | (diff ? 2 : 0) | flip)), msb, lsb);
       }
     }
-    for (int k = 0; k < 8; k++) out[k] = best_blk[k];
+    etc1_store(out, best_blk);
     return;
   }
   if (target == 3 || target == 4) {
     // BC1 (8 bytes) / BC3 (16 bytes) from the decoded texels (round 5; the stock loader's dxtSupported row for UASTC sources,
     // src/lib/KTX2Loader.js:610-618).  Colour: range fit - the corners of the texels' bounding box, the R and B ends swapped where the channel
-    // runs against G (sign of the covariance), pulled in by 1/16 of the range, rounded to RGB565; every texel takes the nearest of the four
-    // palette colours; an opaque BC1 block needs colour0 > colour1 (swap + remap, equal endpoints: index 0).  Alpha (BC3): a BC4 block with
-    // alpha0 = the largest, alpha1 = the smallest alpha of the block, eight-value mode.  Re-fits gated by PSNR against the RGBA32 decode and
-    // checked block by block against the plain references of these rules in tests/transcode_ref.py.
+    // runs against G (sign of the covariance), pulled in by 1/16 of the range; those are colour0 / colour1 of bc1_fit and every texel takes its
+    // own palette entry (the ETC1S path maps its four colours and lets texels follow their selectors).  Alpha (BC3): bc4_fit over the sixteen
+    // alphas.  Re-fits gated by PSNR against the RGBA32 decode and checked block by block against the plain references in tests/transcode_ref.py.
     uint8_t *out = J.out[l] + (target == 4 ? 16 : 8) * (size_t)b;
     if (target == 4) {
-      int a0 = 0, a1 = 255;
-      for (int i = 0; i < 16; i++) { const int a = (int)(px[i] >> 24); a0 = a > a0 ? a : a0; a1 = a < a1 ? a : a1; }
-      unsigned long long bits = 0;
-      if (a0 > a1) for (int i = 0; i < 16; i++) {
-        const int a = (int)(px[i] >> 24); int be = 1 << 30; uint32_t bj = 0;
-        for (int j = 0; j < 8; j++) { const int v = j == 0 ? a0 : (j == 1 ? a1 : ((8 - j) * a0 + (j - 1) * a1) / 7); const int d = v - a; if (d * d < be) { be = d * d; bj = (uint32_t)j; } }
-        bits |= (unsigned long long)bj << (3 * i);
-      }
-      out[0] = (uint8_t)a0; out[1] = (uint8_t)a1;
-      for (int k = 0; k < 6; k++) out[2 + k] = (uint8_t)(bits >> (8 * k));
+      const auto alpha = [&](int i) { return (int)(px[i] >> 24); };
+      int a0, a1; bc4_fit<16>(alpha, 0xffffu, a0, a1);
+      bc4_pack(out, a0, a1, [&](int i) { return bc4_nearest(a0, a1, alpha(i)); });
       out += 8;
     }
     int mn[3] = { 255, 255, 255 }, mx[3] = { 0, 0, 0 }, sum[3] = { 0, 0, 0 };
-    for (int i = 0; i < 16; i++) for (int c = 0; c < 3; c++) { const int v = (int)((px[i] >> (8 * c)) & 255u); mn[c] = v < mn[c] ? v : mn[c]; mx[c] = v > mx[c] ? v : mx[c]; sum[c] += v; }
+    for (int i = 0; i < 16; i++) for (int c = 0; c < 3; c++) { const int v = u_comp(px[i], c); mn[c] = v < mn[c] ? v : mn[c]; mx[c] = v > mx[c] ? v : mx[c]; sum[c] += v; }
     int cov_rg = 0, cov_bg = 0;
     for (int i = 0; i < 16; i++) {
-      const int r = 16 * (int)(px[i] & 255u) - sum[0], g = 16 * (int)((px[i] >> 8) & 255u) - sum[1], bl = 16 * (int)((px[i] >> 16) & 255u) - sum[2];
+      const int r = 16 * u_comp(px[i], 0) - sum[0], g = 16 * u_comp(px[i], 1) - sum[1], bl = 16 * u_comp(px[i], 2) - sum[2];
       cov_rg += (r >> 4) * (g >> 4); cov_bg += (bl >> 4) * (g >> 4);
     }
     int hi[3] = { mx[0], mx[1], mx[2] }, lo[3] = { mn[0], mn[1], mn[2] };
     if (cov_rg < 0) { hi[0] = mn[0]; lo[0] = mx[0]; }
     if (cov_bg < 0) { hi[2] = mn[2]; lo[2] = mx[2]; }
     for (int c = 0; c < 3; c++) { const int ins = (hi[c] - lo[c]) / 16; hi[c] -= ins; lo[c] += ins; }
-    const int q0[3] = { (hi[0] * 31 + 127) / 255, (hi[1] * 63 + 127) / 255, (hi[2] * 31 + 127) / 255 };
-    const int q1[3] = { (lo[0] * 31 + 127) / 255, (lo[1] * 63 + 127) / 255, (lo[2] * 31 + 127) / 255 };
-    uint32_t c0 = (uint32_t)((q0[0] << 11) | (q0[1] << 5) | q0[2]), c1 = (uint32_t)((q1[0] << 11) | (q1[1] << 5) | q1[2]);
-    int pal[4][3];
-    { const int e0[3] = { (q0[0] << 3) | (q0[0] >> 2), (q0[1] << 2) | (q0[1] >> 4), (q0[2] << 3) | (q0[2] >> 2) };
-      const int e1[3] = { (q1[0] << 3) | (q1[0] >> 2), (q1[1] << 2) | (q1[1] >> 4), (q1[2] << 3) | (q1[2] >> 2) };
-      for (int c = 0; c < 3; c++) { pal[0][c] = e0[c]; pal[1][c] = e1[c]; pal[2][c] = (2 * e0[c] + e1[c]) / 3; pal[3][c] = (e0[c] + 2 * e1[c]) / 3; } }
-    uint32_t idx = 0;
-    if (c0 != c1) {
-      const uint32_t flip = c0 < c1 ? 1u : 0u;             // four-colour mode wants colour0 > colour1: swap, 0 <-> 1 and 2 <-> 3
-      for (int i = 0; i < 16; i++) {
-        int be = 1 << 30; uint32_t bj = 0;
-        for (int j = 0; j < 4; j++) { int d = 0; for (int c = 0; c < 3; c++) { const int t = pal[j][c] - (int)((px[i] >> (8 * c)) & 255u); d += t * t; } if (d < be) { be = d; bj = (uint32_t)j; } }
-        idx |= (bj ^ flip) << (2 * i);
-      }
-      if (flip) { const uint32_t t = c0; c0 = c1; c1 = t; }
-    }
-    out[0] = (uint8_t)c0; out[1] = (uint8_t)(c0 >> 8); out[2] = (uint8_t)c1; out[3] = (uint8_t)(c1 >> 8);
-    out[4] = (uint8_t)idx; out[5] = (uint8_t)(idx >> 8); out[6] = (uint8_t)(idx >> 16); out[7] = (uint8_t)(idx >> 24);
+    Bc1Fit F; bc1_fit(hi, lo, F);
+    bc1_pack(out, F.c0, F.c1, [&](int i) { return bc1_nearest(F, u_comp(px[i], 0), u_comp(px[i], 1), u_comp(px[i], 2)); });
     return;
   }
   const uint32_t X = b % J.bx, Y = b / J.bx;
-  for (int y = 0; y < 4 && 4 * Y + (uint32_t)y < J.H; y++) {
-    uint8_t *row = J.out[l] + 4 * ((size_t)(4 * Y + (uint32_t)y) * J.W + 4 * (size_t)X);
-    if (X * 4 + 3 < J.W && (J.W & 3) == 0) *reinterpret_cast<uint4 *>(row) = make_uint4(px[4 * y], px[4 * y + 1], px[4 * y + 2], px[4 * y + 3]);
-    else for (int x = 0; x < 4 && 4 * X + (uint32_t)x < J.W; x++) { const uint32_t v = px[4 * y + x]; row[4 * x] = (uint8_t)v; row[4 * x + 1] = (uint8_t)(v >> 8); row[4 * x + 2] = (uint8_t)(v >> 16); row[4 * x + 3] = (uint8_t)(v >> 24); }
-  }
+  for (int y = 0; y < 4 && 4 * Y + (uint32_t)y < J.H; y++) t_store_row4(J.out[l] + 4 * (size_t)(4 * Y + (uint32_t)y) * J.W, J.W, X, px + 4 * y);
 }
 
 // ================================================================================================
