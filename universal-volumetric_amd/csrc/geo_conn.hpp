@@ -113,9 +113,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_valence_init(GeoJob *jobs) {
 // a run of up to 64 symbols is resolved by the whole wave at once: lane j reads the run-start valence of its vertex
 // and subtracts what lanes k < j apply to that same vertex (one pass of v_readlane broadcasts), then every lane posts
 // its three decrements with atomic adds.  Only an S symbol (vertex split: ring walks + corner re-mapping) is serial.
-__global__ void __launch_bounds__(64) k_eb_valence(GeoJob *jobs) {
-  GeoJob &J = jobs[blockIdx.x];
-  UVOL_SERIAL_PRIO();
+// One wave per frame: the body of k_eb_valence (auxiliary stream) and of the replay row of k_traverse_wave_f16 (geo_walk_simt.hpp).
+__device__ __forceinline__ void eb_valence_frame(GeoJob &J) {
   const uint32_t lane = threadIdx.x;
   const bool ok = J.status == 0;
   const int nsym = ok ? J.nsym : 0, nc = (int)J.nc;
@@ -183,13 +182,15 @@ __global__ void __launch_bounds__(64) k_eb_valence(GeoJob *jobs) {
     }
   }
 }
+__global__ void __launch_bounds__(64) k_eb_valence(GeoJob *jobs) {
+  UVOL_SERIAL_PRIO();
+  eb_valence_frame(jobs[blockIdx.x]);
+}
 
 // symbols -> the six valence-context streams, in symbol order (wave ballots give each symbol its slot).  The streams lie back to back in
 // ONE array of nf entries (six arrays of the worst-case length each were 4.8 MB per 200 k-face frame in flight): a first pass over the
-// contexts counts, the second scatters.
-__global__ void __launch_bounds__(64) k_eb_ctx(GeoJob *jobs) {
-  GeoJob &J = jobs[blockIdx.x];
-  UVOL_SERIAL_PRIO();
+// contexts counts, the second scatters.  One wave per frame, like eb_valence_frame, whose ctx_of[] it reads.
+__device__ __forceinline__ void eb_ctx_frame(GeoJob &J) {
   const uint32_t lane = threadIdx.x;
   const int nsym = J.status == 0 ? J.nsym : 0;
   uint32_t cnt[6] = {0, 0, 0, 0, 0, 0};
@@ -214,6 +215,10 @@ __global__ void __launch_bounds__(64) k_eb_ctx(GeoJob *jobs) {
     }
   }
   if (lane == 0 && J.status == 0) for (int c = 0; c < 6; c++) { J.ctx_n[c] = cnt[c]; J.rs[c].n = cnt[c]; J.ctx_sym[c] = all + (base_c[c] - cnt[c]); J.rs[c].syms = J.ctx_sym[c]; }
+}
+__global__ void __launch_bounds__(64) k_eb_ctx(GeoJob *jobs) {
+  UVOL_SERIAL_PRIO();
+  eb_ctx_frame(jobs[blockIdx.x]);
 }
 
 // ------------------------------------------------------------------------------------------------

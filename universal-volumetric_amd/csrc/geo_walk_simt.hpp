@@ -533,8 +533,26 @@ __device__ __forceinline__ void traverse_wave_f16(GeoJob *jobs, int n, int W, in
     if (t == 0 && J.nverts != 0xffffffffu && (uint32_t)n_ord != J.nverts) J.status = -11;      // (the decode path has no expected count)
   }
 }
-// grid (waves, tables): table t0 + blockIdx.y, walkers blockIdx.x * W .. of that table in lanes 0 .. W - 1
-__global__ void __launch_bounds__(64) k_traverse_wave_f16(GeoJob *jobs, int n, int W, int t0, int base_hi) {
+// The replay row: the valence replay and the context scatter of frame blockIdx.x (geo_conn.hpp), one wave per frame like the kernels
+// k_eb_valence / k_eb_ctx, which run the same two functions on an auxiliary stream.  Both read what the walk left and write arrays no
+// traverser touches (ws_collect: all of them live in the traversals' phase in the late join's layout), so the row needs no order
+// with the traverser rows - only the one between its own two halves: ctx_of[] written by one lane is read by another.  Not inlined:
+// the traverser rows keep the registers and the code they have without it.
+__device__ __attribute__((noinline)) void eb_replay_frame(GeoJob &J) {
+  UVOL_SERIAL_PRIO();
+  eb_valence_frame(J);
+  UVOL_WAVE_FENCE();
+  UVOL_WAVE_SYNC();
+  eb_ctx_frame(J);
+}
+// grid (waves, tables): table t0 + blockIdx.y, walkers blockIdx.x * W .. of that table in lanes 0 .. W - 1; with `replay` one more row
+// behind the nt tables' rows, a block per frame (the grid is as wide as the wider of the two kinds of row: blocks past their row's
+// count leave at once)
+__global__ void __launch_bounds__(64) k_traverse_wave_f16(GeoJob *jobs, int n, int W, int t0, int base_hi, int nt, int replay) {
+  if (replay) {
+    if ((int)blockIdx.y >= nt) { if ((int)blockIdx.x < n) eb_replay_frame(jobs[blockIdx.x]); return; }
+    if ((int)blockIdx.x * W >= n) return;
+  }
   const int t = t0 + (int)blockIdx.y;
   if (t == 0 && base_hi) traverse_wave_f16<3>(jobs, n, W, t); else traverse_wave_f16<1>(jobs, n, W, t);
 }

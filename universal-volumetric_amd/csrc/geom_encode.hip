@@ -73,13 +73,14 @@ struct GeoLane {
   std::vector<const uint8_t *> mats; int frame0 = 0;      // material ids per frame (nullptr: none; empty: no frame has any); index of the group's first frame in its call
   size_t *out_lens = nullptr; int *status = nullptr; int n = 0, n_conc = 0;
   bool late_join = false;  // the group in flight joins its auxiliary stream behind the traversals (geo_submit_impl)
+  bool replay_fused = false; int fmt_trav = 0;      // ... or has no auxiliary stream: its valence replay is a row of the traversal launch; record format of its traversal tables (UVOL_TIMING reports both)
   // GPU-resident form (uvol_encode_mesh_batch_dev_out): the packed output area is the CALLER's device buffer and the payload is not copied out
   uint8_t *ext_out = nullptr; size_t ext_cap = 0; size_t *ext_offs = nullptr; hipStream_t producer = nullptr; hipEvent_t ev_prod = nullptr;
   std::chrono::steady_clock::time_point t_enter; double t_prep = 0, t_enq = 0;
 };
 struct GeoState {
   std::vector<GeoLane *> lanes; int next_lane = 0;
-  hipStream_t aux = nullptr;           // the lanes' shared auxiliary stream, where the queue budget has no room for one per lane (geo_ring, uvol_ws.hpp); created with the first lane, destroyed behind the last
+  hipStream_t aux = nullptr;           // the lanes' shared auxiliary stream, where the queue budget has no room for one per lane (geo_ring, uvol_ws.hpp); created by the first group that needs it (geo_shared_aux), destroyed behind the last lane
   int lanes_cap = 1 << 20;             // lanes the ring may use: lowered when a lane could not get its workspace (three lanes of general-layout groups do not fit beside a full set of inputs), reset by uvol_trim
   hipEvent_t walk_last = nullptr;      // walk event of the group submitted last (UVOL_GEO_CHAIN=2)
   hipEvent_t fe_last = nullptr;        // front-end event of the group submitted last (the front ends of consecutive groups run one after the other)
@@ -118,7 +119,7 @@ static GeoLane *geo_lane(uvol_ctx *ctx, int k) {
     GeoLane *L = new GeoLane();
     if (G->lanes.empty()) L->stream = ctx->stream; else { if (uvol_make_stream(ctx, &L->stream) != hipSuccess) { delete L; return nullptr; } L->own_stream = true; }
     hipError_t ea = hipSuccess;
-    if (geo_ring().shared_aux) L->aux = G->aux;      // (nullptr until the first submission: geo_shared_aux)
+    if (geo_ring().shared_aux) L->aux = G->aux;      // (nullptr until a group needs it: geo_shared_aux)
     else { ea = uvol_make_stream(ctx, &L->aux); L->own_aux = ea == hipSuccess; }
     if (ea != hipSuccess || hipEventCreate(&L->ev_walk) != hipSuccess || hipEventCreate(&L->ev_val) != hipSuccess ||
         hipEventCreateWithFlags(&L->ev_fe, hipEventDisableTiming) != hipSuccess) { geo_lane_free(L); return nullptr; }
@@ -126,7 +127,8 @@ static GeoLane *geo_lane(uvol_ctx *ctx, int k) {
   }
   return G->lanes[k];
 }
-// The shared auxiliary stream is created with the first submission, BEHIND the main streams of all lanes of the ring: the runtime deals
+// The shared auxiliary stream is created when a group first needs it (geo_submit_impl: a group whose replay is fused into its traversal
+// launch does not, and a process that only ever runs such groups never has the stream), BEHIND the main streams of all lanes of the ring: the runtime deals
 // streams to its hardware queues in the order of their creation (a new queue while the budget has one, then the queue with the fewest
 // streams), so the main streams take queues of their own first and the auxiliary stream takes what is left - on a budget that the ring
 // fills, a queue that one main stream holds already.  Created first it took a queue for itself and two main streams met on another
@@ -209,6 +211,9 @@ enum { PH_DEDUP = 0, PH_FACES, PH_CT, PH_FANS0, PH_DENSE0, PH_WALK, PH_FTIME, PH
 // where the planner's total is smallest: a 200 k-face frame of a large batch (compact layout, per-face records) holds 29.2 MB with the
 // early join, about 34 MB with the late join here, 35.7 MB behind k_v2d and 36.0 MB before k_hist (the entries' order and inverse maps,
 // then the symbol arrays, would have to keep clear of the replay's inputs too).
+// The FUSED replay (a row of the traversal launch, geo_submit_impl) rests on the same layout: what the replay reads and writes (opp,
+// face_time, proc, symb, vval, c2vm, ctx_of, ctx_all) is live in PH_TRAV, like everything a traverser reads or writes there (rec[], tstart,
+// order[], t_stack[]; t_vvis[] is pinned), and arrays that are live in one phase never share bytes.
 constexpr int GEO_LATE_JOIN_PHASE = PH_TRAV;
 
 // Collects the arrays of job J (sizes from its input counts) and sets the capacities stored in J.  full = worst-case sizes.
@@ -494,15 +499,26 @@ static inline bool geo_rec8(uint32_t max_nfi, uint64_t max_ids) {
 // the decode path sizes its record tables with the same rule; its vertex ids are dense (< 3 * faces)
 bool geo_records8(uint32_t max_nfi) { return geo_rec8(max_nfi, 3ull * max_nfi); }
 static inline bool geo_rec_face_off() { static const bool v = [] { const char *e = getenv("UVOL_REC_FACE"); return e && *e == '0'; }(); return v; }      // UVOL_REC_FACE=0 (diagnostic, tests): corner records in the lane-per-walker kernels too
-static void launch_traversals(uvol_ctx *ctx, GeoJob *dj, int n, const WalkPlan &P, int r8, int base_hi = 0) {
+// UVOL_TRAV_FORM=lane (tests, diagnostic): the lane-per-walker kernel whose idle lanes leave the loop; default: the wave form
+// (k_traverse_wave_f16: pops as ordinary steps, component search by the whole wave)
+static inline bool geo_trav_lane_form() { static const bool v = [] { const char *e = getenv("UVOL_TRAV_FORM"); return e && !strcmp(e, "lane"); }(); return v; }
+// the traversers of plan P on records of format r8 run in the wave form: the kernel that can carry the replay row
+static inline bool geo_trav_wave_form(const WalkPlan &P, int r8) { return P.simt_w && r8 == 2 && !geo_trav_lane_form(); }
+// UVOL_REPLAY=aux|fused (tests, A/B runs): the valence replay on the auxiliary stream / as a row of the traversal launch, wherever
+// that form is legal (geo_submit_impl); unset: the fused form where it is legal
+static inline int geo_replay_env() { static const int v = [] { const char *e = getenv("UVOL_REPLAY"); return !e ? -1 : (!strcmp(e, "aux") ? 0 : (!strcmp(e, "fused") ? 1 : -1)); }(); return v; }
+// replay: the wave form's launch carries the valence replay of the n frames as one more row of workgroups (k_traverse_wave_f16)
+static void launch_traversals(uvol_ctx *ctx, GeoJob *dj, int n, const WalkPlan &P, int r8, int base_hi = 0, bool replay = false) {
   const unsigned N = (unsigned)n;
   if (P.simt_w) {
     const unsigned W = (unsigned)P.simt_w, nb = (3 * N + W - 1) / W;
-    // UVOL_TRAV_FORM=lane (tests, diagnostic): the lane-per-walker kernel whose idle lanes leave the loop; default: the wave form
-    // (k_traverse_wave_f16: pops as ordinary steps, component search by the whole wave), UVOL_TRAV_W lanes per wave
-    static const bool lane_form = [] { const char *e = getenv("UVOL_TRAV_FORM"); return e && !strcmp(e, "lane"); }();
+    // UVOL_TRAV_W: lanes per wave of the wave form
     static const int wave_w = [] { const char *e = getenv("UVOL_TRAV_W"); const int v = e ? atoi(e) : 0; return v < 0 ? 0 : (v > 64 ? 64 : v); }();
-    if (r8 == 2 && !lane_form) { const unsigned Ww = wave_w ? (unsigned)wave_w : W; LAUNCH(k_traverse_wave_f16, dim3((N + Ww - 1) / Ww, 3), dim3(64), dj, n, (int)Ww, 0, base_hi); }
+    if (geo_trav_wave_form(P, r8)) {
+      const unsigned Ww = wave_w ? (unsigned)wave_w : W, waves = (N + Ww - 1) / Ww;
+      if (replay) LAUNCH(k_traverse_wave_f16, dim3(std::max(waves, N), 4), dim3(64), dj, n, (int)Ww, 0, base_hi, 3, 1);
+      else LAUNCH(k_traverse_wave_f16, dim3(waves, 3), dim3(64), dj, n, (int)Ww, 0, base_hi, 3, 0);
+    }
     else if (r8 == 2) LAUNCH(k_traverse_simt_f16, dim3(nb), dim3(64), dj, n, (int)W, 0, 3);
     else if (r8) LAUNCH((k_traverse_simt<true>), dim3(nb), dim3(64), dj, n, (int)W); else LAUNCH((k_traverse_simt<false>), dim3(nb), dim3(64), dj, n, (int)W);
   }
@@ -704,7 +720,7 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
   };
   if (late_env < 0 && !late_small && !seq) late_join = ring_fits_late();
 #endif
-  L.late_join = late_join;
+  L.late_join = late_join; L.replay_fused = false;
   auto lay = [&]() -> int {
   L.hjobs.assign((size_t)n, GeoJob{});
   ws_total = 0; in_total = 0; out_total = 0; max_ecap = 0; he_nb_max = 0; ms_nb_max = 1; he_part_all = true; algo_in = 0;
@@ -960,12 +976,24 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     LAUNCH(k_valence_init, dim3(bc, N), dim3(UVOL_BLOCK), dj);
   }
   UVOL_HIP_CHECK(ctx, hipEventRecord(L.ev_walk, ctx->stream)); G->walk_last = L.ev_walk;
-  UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(L.aux, L.ev_walk, 0));
-  {
-    { uvol_ctx::Scope sc(ctx, "geo.k4_eb_valence", 0, L.aux); LAUNCH_ON(L.aux, k_eb_valence, dim3(N), dim3(64), dj); }
-    LAUNCH_ON(L.aux, k_eb_ctx, dim3(N), dim3(64), dj);
+  // FUSED replay: where the join would be late and the traversers run in the wave form (the large calls of the bench), the replay is a row
+  // of workgroups of the traversal launch (k_traverse_wave_f16) instead: it has the traversers' block shape, depends on less than they do
+  // and is shorter (~50 against ~220 ms), and it then takes no stream - on a queue budget that the ring's main streams fill, the shared
+  // auxiliary stream sat on one main stream's queue, where replays and that lane's kernels waited for each other (DESIGN section 5,
+  // profiles/r16_fused_replay.json).  The late join's layout keeps what the replay reads and writes apart from everything live in the
+  // traversals' phase (GEO_LATE_JOIN_PHASE), which is what one launch needs.  The early join (its layout lets the record tables lie on the
+  // replay's inputs), the LDS walkers of small calls and the lane form keep the auxiliary stream.  UVOL_REPLAY=aux forces the stream.
+  const bool replay_fused = late_join && geo_trav_wave_form(wp_trav, fmtT) && geo_replay_env() != 0;
+  L.replay_fused = replay_fused; L.fmt_trav = fmtT;
+  if (!replay_fused) {
+    if ((rc = geo_shared_aux(ctx))) return rc;              // (the shared stream is created when a group first needs it)
+    UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(L.aux, L.ev_walk, 0));
+    {
+      { uvol_ctx::Scope sc(ctx, "geo.k4_eb_valence", 0, L.aux); LAUNCH_ON(L.aux, k_eb_valence, dim3(N), dim3(64), dj); }
+      LAUNCH_ON(L.aux, k_eb_ctx, dim3(N), dim3(64), dj);
+    }
+    UVOL_HIP_CHECK(ctx, hipEventRecord(L.ev_val, L.aux));
   }
-  UVOL_HIP_CHECK(ctx, hipEventRecord(L.ev_val, L.aux));
   // (Seam flags and attribute vertices - k_seams, k_aseg_a, k_aseg_b - read the stored tables only, not the walk's output, and were
   // tried on the auxiliary stream BESIDE the walk: slower in both forms of the join, 2632 - 2691 against 2733 - 2765 frames/s early;
   // the walk is the chain's latency-bound link and pays for streaming neighbours.  DESIGN section 5, "measured and not kept".)
@@ -995,9 +1023,9 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     // (blocking calls only: enqueued calls run beside their predecessors' groups - a stream of 300-frame jobs lost 4 % with one per wave)
     if (wp_trav.simt_w > 1 && !lockstep && geo_simt_env() == 0) wp_trav.simt_w = fmtT == 2 ? ((G->blocking_call && 3u * NC <= 2048u) ? 1 : ((G->blocking_call && 3u * NC <= 4096u) ? 2 : 4)) : 1;
     if (w_trav_env && wp_trav.simt_w) wp_trav.simt_w = w_trav_env;
-    launch_traversals(ctx, dj, n, wp_trav, fmtT, base_shared ? 1 : 0);
+    launch_traversals(ctx, dj, n, wp_trav, fmtT, base_shared ? 1 : 0, replay_fused);      // (fused: geo.k4_eb_valence has no bracket of its own, its time is in this one)
   }
-  if (late_join) UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, L.ev_val, 0));      // (GEO_LATE_JOIN_PHASE: what is born from k_v2d on may lie where the replay's inputs were)
+  if (late_join && !replay_fused) UVOL_HIP_CHECK(ctx, hipStreamWaitEvent(ctx->stream, L.ev_val, 0));      // (GEO_LATE_JOIN_PHASE: what is born from k_v2d on may lie where the replay's inputs were)
   { uvol_ctx::Scope sc(ctx, "geo.k5b_v2d", 0); LAUNCH(k_v2d, dim3(be, N, 3), dim3(UVOL_BLOCK), dj, fmtT); }      // (own scope: geo.k5_traverse is exactly the traversal kernel, as rocprof lists it)
   {
     uvol_ctx::Scope sc(ctx, "geo.k6_predict", 0);
@@ -1149,7 +1177,7 @@ static int geo_complete_impl(uvol_ctx *ctx, GeoLane &L) {
       if (st1 != UVOL_OK) worst = st1;
     }
   }
-  if (timing) fprintf(stderr, "[uvol-timing] geo group n=%d sizeof(GeoJob)=%zu %s join: host prepared %.1f ms, enqueued %.1f, gpu done %.1f, packed d2h %.1f, copied out %.1f (enter at %.1f)\n", n, sizeof(GeoJob), late_join ? "late" : "early", t_prep, t_enq, t_gpu, t_d2h, ms_since(t_enter),
+  if (timing) fprintf(stderr, "[uvol-timing] geo group n=%d sizeof(GeoJob)=%zu %s join, %s replay, traversal records %d: host prepared %.1f ms, enqueued %.1f, gpu done %.1f, packed d2h %.1f, copied out %.1f (enter at %.1f)\n", n, sizeof(GeoJob), late_join ? "late" : "early", L.replay_fused ? "fused" : "aux", L.fmt_trav, t_prep, t_enq, t_gpu, t_d2h, ms_since(t_enter),
                       std::chrono::duration<double, std::milli>(t_enter.time_since_epoch()).count());
   return status ? UVOL_OK : worst;
 }
@@ -1162,8 +1190,7 @@ static int geo_submit(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, int n,
   L.meshes.assign(meshes, meshes + n); L.outp.assign(outs, outs + n); L.caps.assign(caps, caps + n);
   L.out_lens = out_lens; L.status = status; L.n = n; L.n_conc = n_conc; L.on_device = on_device; L.full = full;
   hipStream_t saved = ctx->stream; ctx->stream = L.stream;
-  int rc = geo_shared_aux(ctx);
-  if (rc == UVOL_OK) rc = geo_submit_impl(ctx, L, L.meshes.data(), n, n_conc, on_device, L.caps.data(), full);
+  int rc = geo_submit_impl(ctx, L, L.meshes.data(), n, n_conc, on_device, L.caps.data(), full);
   ctx->stream = saved;
   if (rc != UVOL_OK && L.up.slot) { (void)hipStreamSynchronize(L.stream); if (L.aux) (void)hipStreamSynchronize(L.aux); L.up.slot = nullptr; }      // (kernels already enqueued may read the slot: its release was never recorded)
   L.busy = rc == UVOL_OK;
