@@ -194,12 +194,73 @@ int uvol_png_status(uvol_ctx *ctx, int slot, int *status, int n);
  * Blocking: like the other blocking entry points it first waits for the context's enqueued calls - so a slot an enqueued encode still reads
  * is never overwritten - and returns when the layers are complete.  There is NO host-output form (the layers exist to be encoded from HBM)
  * and NO enqueue form (the kernel moves 17 MB per 2048^2 layer once; the encode that follows is what takes time).  uvol_trim gives the slots
- * back, uvol_ctx_destroy frees them.  Mip levels inside one .ktx2 stay out of scope; the kernel is what they would use.
+ * back, uvol_ctx_destroy frees them.  Mip levels inside one .ktx2 are made by uvol_mipchain_rgba_batch_dev below, with this filter.
  * UVOL_E_INVALID with a message, before anything runs: a factor other than 2 / 4 / 8, a slot other than 0 / 1, a NULL layer (or a device
  * layer that is not 4-byte aligned), width or height zero or beyond the limits of uvol_unfilter_png_batch_dev (8192 x 16384).  n <= 0 is
  * UVOL_OK and does nothing. */
 int uvol_downscale_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height,
                                   int inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
+
+/* ---- mip levels inside one UASTC .ktx2 (additive: uvol_abi_version stays 1) ----
+ * A compressed texture cannot get mip levels at load time: the stock loader turns trilinear filtering on only for a file that carries more
+ * than one level (reference src/lib/KTX2Loader.js:279) and transcodes every (mip, layer) the file has (:516-570).  The reduced-resolution
+ * targets above are separate files a player picks between, not levels of one texture.
+ *
+ * uvol_mip_level_count: floor(log2(max(width, height))) + 1, the length of the full chain (level 0 included); 0 for an empty image.
+ *
+ * uvol_mipchain_rgba_batch_dev: n RGBA8 layers of width x height (top row first) become levels 1 .. levels - 1 of each layer in ONE pass over
+ * level 0; rgba_dev_out[i * (levels - 1) + (v - 1)] is a DEVICE pointer to level v of layer i, in the context's CHAIN slot `slot` (0 / 1; the
+ * chain slots are not the downscale slots: a ladder rung and a chain coexist), valid until that slot is written again.  levels == 0 means the
+ * full chain (rgba_dev_out then holds n * (uvol_mip_level_count(width, height) - 1) entries).  inputs_on_device as for the downscale: device
+ * pointers (4-byte aligned; layers of a PNG ingest slot are ordered behind their un-filter) or host memory uploaded through the staging buffers.
+ * The filter (normative) is the one of uvol_downscale_rgba_batch_dev with a box of any size:
+ *   level v is lw x lh with lw = max(1, width >> v), lh = max(1, height >> v);
+ *   fx = width / lw and fy = height / lh must be exact integers - always so for powers of two, and for width = 2^a m up to v = a -; otherwise
+ *   the call is UVOL_E_INVALID with a message naming the level and the size, before anything runs;
+ *   output texel (X, Y) of level v is made in ONE step from the n = fx fy texels of level 0 with fx X <= x < fx X + fx, fy Y <= y < fy Y + fy, by
+ *   exactly the lin[], alpha, alpha-weighted colour and nearest-v rules above (A = sum a, out.a = (2 A + n) / (2 n); N = sum lin[c] a, D = A - or,
+ *   when A == 0, N = sum lin[c], D = n -, m = (2 N + D) / (2 D), out.c = the v with the smallest |lin[v] - m|, the lower v at a tie).
+ * So for v <= 3 the result is bit-identical to uvol_downscale_rgba_batch_dev at factor 2^v.  The sums A, sum lin a and sum lin are additive
+ * over boxes, so the device computes a level from the sums of finer levels with the same result as from level 0, and reads level 0 once
+ * (sums are 64-bit from the 16 x 16 box on; csrc/tex_mipchain.hip).
+ * Blocking: it first waits for the context's enqueued calls and returns when the levels are complete; there is no enqueue form.  uvol_trim
+ * gives the slots back, uvol_ctx_destroy frees them.  UVOL_E_INVALID with a message, before anything runs: the refusals of the downscale (a
+ * NULL layer, a device layer that is not 4-byte aligned, a slot other than 0 / 1, width or height zero or beyond 8192 x 16384), levels < 0,
+ * levels > uvol_mip_level_count(width, height), a level that fails the divisibility rule.  levels == 1 and n <= 0 are UVOL_OK and do nothing.
+ * Profile groups: ingest.mipchain (and ingest.mipchain_upload for host inputs). */
+int uvol_mip_level_count(uint32_t width, uint32_t height);
+int uvol_mipchain_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height,
+                                 int inputs_on_device, int levels, int slot, const uint8_t **rgba_dev_out);
+
+/* uvol_encode_texture_segments_mips: the semantics of uvol_encode_texture_segments_st (per-segment status[], host or device inputs) with mip
+ * levels.  In a context created with uvol_params.uastc = 1 every segment becomes ONE .ktx2 with levelCount = levels (0 = the full chain):
+ * level 0 as uvol_encode_texture_segments_st encodes it, then the chain above on the context's stream (in a slot of its own, not the caller's
+ * two), then the UASTC encode of every level; the context's y_flip applies to each level's own height.  A UASTC level is nothing but its
+ * layers' blocks, so level v of the file is byte for byte the level data of a single-level file encoded from the level-v images.  Container:
+ * levelCount in the header, one level-index entry of 24 bytes per level from byte 80 on (level 0 first), DFD and key-value offsets moved
+ * accordingly, level data stored smallest level first, every level 16-byte aligned, inside a level the layers in order with
+ * ceil(lw / 4) ceil(lh / 4) blocks of 16 bytes each, byteLength == uncompressedByteLength, KTXanimData and the DFD as in the single-level file,
+ * the alpha channel id set when any level has a block with alpha.  levels == 1 gives the bytes of uvol_encode_texture_segments_st.  The
+ * divisibility rule of the chain applies (UVOL_E_INVALID before anything runs).  In an ETC1S context (uastc = 0) levels != 1 is
+ * UVOL_E_UNSUPPORTED before anything runs: "mip levels are written in the UASTC mode only" - the ETC1S pipeline has
+ * one slice geometry for all slices.  There is NO enqueue form.  uvol_texture_bound_mips: the size that always suffices for outs[s]. */
+size_t uvol_texture_bound_mips(uint32_t width, uint32_t height, int n_layers, int levels);
+int uvol_encode_texture_segments_mips(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers,
+                                      uint32_t width, uint32_t height, int inputs_on_device, int levels,
+                                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
+
+/* Reading them.  uvol_ktx2_levels (host-only): the level count of a file uvol_ktx2_info accepts - a UASTC file's levelCount, after every
+ * entry of its level index has been checked against the file size and against layers x blocks(level) x 16; 1 for an ETC1S file.
+ * uvol_transcode_texture_segments_level: uvol_transcode_texture_segments_st for mip level `level` of every file: outs[s * layers + l] receives
+ * that level of layer l at the LEVEL's size (max(1, width >> level) x max(1, height >> level); layer_cap sized for it), for every UVOL_TARGET_*
+ * a UASTC source takes - what transcodeImage(dst, mip, layer, ...) gives the stock loader.  A file whose count is <= level is UVOL_E_INVALID in
+ * its own status; an ETC1S file has one level: level 0 behaves as uvol_transcode_texture_segments_st, any other is UVOL_E_INVALID for that
+ * segment.  The decode / transcode entry points without a level argument and uvol_ktx2_info accept a multi-level UASTC file and mean level 0.
+ * Zstandard-supercompressed multi-level UASTC files carry one frame per level; each is inflated under the bounds of the single-level case.
+ * Multi-level ETC1S (stock `basisu -mipmap` without -uastc) stays UVOL_E_UNSUPPORTED, with a message that names it. */
+int uvol_ktx2_levels(const uint8_t *ktx2, size_t len, uint32_t *levels);
+int uvol_transcode_texture_segments_level(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, int level,
+                                          uint8_t *const *outs, size_t layer_cap, int target, int outputs_on_device, int *status);
 
 /* ---- the raw `etc2` texture target from source texels (additive: uvol_abi_version stays 1) ----
  * The player's raw `etc2` target is uncompressed block data, one file per frame at 8 bytes per 4x4 block, for the devices that cannot afford

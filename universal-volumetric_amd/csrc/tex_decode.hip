@@ -595,6 +595,8 @@ int tex_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t
   std::vector<size_t> foff((size_t)n);
   for (int i = 0; i < n; i++) {
     const int rc = tdec_parse(files[i], lens[i], T->hjobs[i]);
+    if (rc == -2 && lens[i] >= 104 && rd32h(files[i] + 40) > 1 && rd32h(files[i] + 44) == 1) {      // stock `basisu -mipmap` without -uastc
+      ctx->set_error("segment %d: a multi-level ETC1S .ktx2 (%u mip levels): mip levels are read from UASTC files only (DESIGN.md section 7)", i, rd32h(files[i] + 40)); return UVOL_E_UNSUPPORTED; }
     if (rc) { ctx->set_error("segment %d: not a KTX2 / BasisLZ ETC1S file this decoder supports (parse code %d)", i, rc); return rc == -2 || rc == -6 ? UVOL_E_UNSUPPORTED : UVOL_E_INVALID; }
     if (T->hjobs[i].width != T->hjobs[0].width || T->hjobs[i].height != T->hjobs[0].height || T->hjobs[i].layers != T->hjobs[0].layers || T->hjobs[i].ashift != T->hjobs[0].ashift) { ctx->set_error("segment %d: size / layer count differs from segment 0", i); return UVOL_E_INVALID; }
     foff[i] = files_total; files_total += (lens[i] + 16 + 255) & ~(size_t)255;

@@ -27,8 +27,6 @@
 #include <cmath>
 
 #define DOWN_BLOCK 256
-#define DOWN_BUCKETS 4096                               /* m >> 4, m <= 65535 */
-#define DOWN_TABLE_WORDS (512 + DOWN_BUCKETS / 4)
 
 // one input texel into the sums of its output texel; lin = the table's copy of this lane (REP words per entry)
 template <int REP>
@@ -116,8 +114,8 @@ __global__ void __launch_bounds__(DOWN_BLOCK) k_downscale(const uint8_t *const *
 struct DownState { uvol_devbuf out[2], in, ptrs, tables; bool tables_up = false; std::vector<const uint8_t *> hptrs; uint32_t htab[DOWN_TABLE_WORDS]; };
 // lin[], mid[] and base[] (see the head of this file); lin is strictly increasing (smallest step 19) and no value lies closer than 0.0016 to
 // a rounding boundary, so the libm in use cannot change an entry.  false: the bucket form of the search disagrees with the plain count for
-// some m (it cannot, with this table: the check is what makes that a fact of the build at hand)
-static bool down_tables(uint32_t *t) {
+// some m (it cannot, with this table: the check is what makes that a fact of the build at hand).  Shared with tex_mipchain.hip.
+bool down_tables(uint32_t *t) {
   for (int v = 0; v < 256; v++) {
     const double s = v / 255.0, L = s <= 0.04045 ? s / 12.92 : std::pow((s + 0.055) / 1.055, 2.4);
     t[v] = (uint32_t)std::floor(65535.0 * L + 0.5);

@@ -644,50 +644,75 @@ namespace {
 inline void uput32(uint8_t *&p, uint32_t v) { memcpy(p, &v, 4); p += 4; }
 inline void uput64(uint8_t *&p, uint64_t v) { memcpy(p, &v, 8); p += 8; }
 inline void uput16(uint8_t *&p, uint16_t v) { memcpy(p, &v, 2); p += 2; }
-// KTX2 header + DFD (colour model 166 = UASTC, BT.709, sRGB, 16-byte 4x4 texel blocks) + key/value data; returns the level offset
-size_t uastc_header(uint8_t *out, uint32_t W, uint32_t H, uint32_t L, bool alpha, uint64_t lvl_len) {
+// KTX2 header + level index + DFD (colour model 166 = UASTC, BT.709, sRGB, 16-byte 4x4 texel blocks) + key/value data.  The fields' places
+// are those the reference's src/lib/ktx-parse.module.js read() / write() use: levelCount at byte 40, the level index at byte 80 with one
+// (byteOffset, byteLength, uncompressedByteLength) entry of 24 bytes per level, level 0 first, the DFD behind the index.  Level data are stored
+// smallest level first, every level 16-byte aligned (a level is a multiple of 16 bytes, so only the first needs padding).  lvl_len[v] = the
+// bytes of level v; lvl_off[v] (may be nullptr) receives its offset; returns the end of the file.  out == nullptr: offsets only.
+size_t uastc_header(uint8_t *out, uint32_t W, uint32_t H, uint32_t L, bool alpha, int levels, const uint64_t *lvl_len, uint64_t *lvl_off) {
   static const uint8_t ident[12] = { 0xAB, 'K', 'T', 'X', ' ', '2', '0', 0xBB, '\r', '\n', 0x1A, '\n' };
   static const char writer[] = "uvol-mi355x uastc 0.1";
   uint8_t kvd[128]; uint8_t *kp = kvd;
   uput32(kp, 12 + 12); memcpy(kp, "KTXanimData", 12); kp += 12; uput32(kp, 1); uput32(kp, 15); uput32(kp, 0);
   uput32(kp, 10 + (uint32_t)sizeof(writer)); memcpy(kp, "KTXwriter", 10); kp += 10; memcpy(kp, writer, sizeof(writer)); kp += sizeof(writer);
   while ((kp - kvd) & 3) *kp++ = 0;
-  const uint32_t dfd_off = 80 + 24, dfd_len = 44, kvd_off = dfd_off + dfd_len, kvd_len = (uint32_t)(kp - kvd);
-  const uint64_t lvl_off = ((uint64_t)kvd_off + kvd_len + 15) & ~15ull;
-  if (!out) return (size_t)lvl_off;
+  const uint32_t dfd_off = 80 + 24 * (uint32_t)levels, dfd_len = 44, kvd_off = dfd_off + dfd_len, kvd_len = (uint32_t)(kp - kvd);
+  const uint64_t data_off = ((uint64_t)kvd_off + kvd_len + 15) & ~15ull;
+  uint64_t offs[UVOL_MIP_MAX_LEVELS], end = data_off;
+  for (int v = levels - 1; v >= 0; v--) { offs[v] = end; end += lvl_len[v]; }
+  if (lvl_off) for (int v = 0; v < levels; v++) lvl_off[v] = offs[v];
+  if (!out) return (size_t)end;
   uint8_t *p = out;
   memcpy(p, ident, 12); p += 12;
-  uput32(p, 0); uput32(p, 1); uput32(p, W); uput32(p, H); uput32(p, 0); uput32(p, L); uput32(p, 1); uput32(p, 1); uput32(p, 0);
+  uput32(p, 0); uput32(p, 1); uput32(p, W); uput32(p, H); uput32(p, 0); uput32(p, L); uput32(p, 1); uput32(p, (uint32_t)levels); uput32(p, 0);
   uput32(p, dfd_off); uput32(p, dfd_len); uput32(p, kvd_off); uput32(p, kvd_len); uput64(p, 0); uput64(p, 0);
-  uput64(p, lvl_off); uput64(p, lvl_len); uput64(p, lvl_len);
+  for (int v = 0; v < levels; v++) { uput64(p, offs[v]); uput64(p, lvl_len[v]); uput64(p, lvl_len[v]); }
   uput32(p, 44); uput32(p, 0); uput16(p, 2); uput16(p, 40);
   *p++ = 166; *p++ = 1; *p++ = 2; *p++ = 0; *p++ = 3; *p++ = 3; *p++ = 0; *p++ = 0;
   *p++ = 16; for (int i = 0; i < 7; i++) *p++ = 0;
   uput16(p, 0); *p++ = 127; *p++ = alpha ? 3 : 0; *p++ = 0; *p++ = 0; *p++ = 0; *p++ = 0; uput32(p, 0); uput32(p, 0xFFFFFFFFu);
   memcpy(p, kvd, kvd_len); p += kvd_len;
-  while ((uint64_t)(p - out) < lvl_off) *p++ = 0;
-  return (size_t)lvl_off;
+  while ((uint64_t)(p - out) < data_off) *p++ = 0;
+  return (size_t)end;
+}
+// the single-level file: returns the level's offset
+size_t uastc_header(uint8_t *out, uint32_t W, uint32_t H, uint32_t L, bool alpha, uint64_t lvl_len) {
+  uint64_t off = 0; (void)uastc_header(out, W, H, L, alpha, 1, &lvl_len, &off); return (size_t)off;
 }
 }  // namespace
 
-// container fields of a UASTC .ktx2 this codec reads (vkFormat 0, DFD model 166, no supercompression, 1 level, 1 face)
-int uastc_ktx2_probe(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint64_t *lvl_off) {
+// container fields of a UASTC .ktx2 this codec reads (vkFormat 0, DFD model 166, no supercompression, 1 face, 1 .. 15 levels).  Every level
+// of the index is checked: its place against the file size, its length against layers x blocks(level) x 16 (and uncompressedByteLength
+// against byteLength).  lvl_offs (may be nullptr): UVOL_MIP_MAX_LEVELS entries, the offset of every level.
+int uastc_ktx2_probe_levels(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint32_t *levels, uint64_t *lvl_offs) {
   static const uint8_t ident[12] = { 0xAB, 'K', 'T', 'X', ' ', '2', '0', 0xBB, '\r', '\n', 0x1A, '\n' };
   if (!b || n < 104 + 44 || n > 0xffffffffull * 16 || memcmp(b, ident, 12)) return -1;
   uint32_t u[9]; memcpy(u, b + 12, 36);
   uint32_t dfd_off, dfd_len; memcpy(&dfd_off, b + 48, 4); memcpy(&dfd_len, b + 52, 4);
   const bool model_uastc = dfd_len >= 44 && dfd_off <= n && dfd_len <= n - dfd_off && b[dfd_off + 12] == 166;
-  // stock `basisu -uastc -ktx2` writes Zstandard-supercompressed level data (scheme 2) by default: recognised, not decoded (no Zstd here)
+  // stock `basisu -uastc -ktx2` writes Zstandard-supercompressed level data (scheme 2) by default: recognised here, inflated by uastc_unzstd
   if (model_uastc && u[0] == 0 && u[8] != 0) return UASTC_PROBE_SUPERCOMPRESSED;
-  if (u[0] != 0 || u[8] != 0 || u[7] != 1 || u[6] != 1 || !u[2] || !u[3] || u[2] > 16384 || u[3] > 16384) return -2;
+  if (u[0] != 0 || u[8] != 0 || u[7] < 1 || u[6] != 1 || !u[2] || !u[3] || u[2] > 16384 || u[3] > 16384) return -2;
   if (!model_uastc) return -3;
-  uint64_t lo, ll; memcpy(&lo, b + 80, 8); memcpy(&ll, b + 88, 8);
-  const uint32_t layers = u[5] ? u[5] : 1;
+  const uint32_t layers = u[5] ? u[5] : 1, nlev = u[7];
   if (layers > 64) return -4;
-  const uint64_t need = (uint64_t)layers * ((u[2] + 3) / 4) * ((u[3] + 3) / 4) * 16;
-  if (lo > n || ll > n - lo || ll != need) return -4;
-  *W = u[2]; *H = u[3]; *L = layers; *lvl_off = lo;
+  if ((int)nlev > mip_level_count(u[2], u[3]) || (uint64_t)80 + 24ull * nlev > n || dfd_off < 80 + 24 * nlev) return -4;      // a level index cut short, or one the DFD overlaps
+  for (uint32_t v = 0; v < nlev; v++) {
+    uint64_t lo, ll, lu; memcpy(&lo, b + 80 + 24 * v, 8); memcpy(&ll, b + 88 + 24 * v, 8); memcpy(&lu, b + 96 + 24 * v, 8);
+    const uint32_t lw = std::max(1u, u[2] >> v), lh = std::max(1u, u[3] >> v);
+    const uint64_t need = (uint64_t)layers * ((lw + 3) / 4) * ((lh + 3) / 4) * 16;
+    if (lo > n || ll > n - lo || ll != need || (nlev > 1 && lu != ll)) return -4;      // (single-level files were never asked for uncompressedByteLength)
+    if (lvl_offs) lvl_offs[v] = lo;
+  }
+  *W = u[2]; *H = u[3]; *L = layers; *levels = nlev;
   return 0;
+}
+// the same, level 0 only: what the decode / transcode entry points without a level argument read
+int uastc_ktx2_probe(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint64_t *lvl_off) {
+  uint64_t offs[UVOL_MIP_MAX_LEVELS]; uint32_t nlev = 0;
+  const int r = uastc_ktx2_probe_levels(b, n, W, H, L, &nlev, offs);
+  if (r == 0) *lvl_off = offs[0];
+  return r;
 }
 
 // Zstandard-supercompressed UASTC (supercompressionScheme 2: what stock `basisu -uastc -ktx2` writes by default; KTX 2.0: every level's data
@@ -697,22 +722,30 @@ int uastc_ktx2_probe(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint3
 // take as any other.  0: `out` holds that file; 1: no libzstd on this machine (the caller refuses the file as before); < 0: not such a file /
 // corrupt frame / sizes that do not match the header.
 // header of such a file: sizes and the level's place, checked against each other (no inflation)
-static int uastc_zstd_header(const uint8_t *b, size_t n, uint32_t &w, uint32_t &h, uint32_t &layers, uint64_t &lo, uint64_t &ll, uint64_t &need) {
+// (since the mip levels: one Zstandard frame per level, every level checked in the same way)
+struct UZstdHead { uint32_t w, h, layers, levels; uint64_t lo[UVOL_MIP_MAX_LEVELS], ll[UVOL_MIP_MAX_LEVELS], need[UVOL_MIP_MAX_LEVELS]; uint64_t head; };
+static int uastc_zstd_header(const uint8_t *b, size_t n, UZstdHead &Z) {
   if (!b || n < 104 + 44) return -1;
   uint32_t u[9]; memcpy(u, b + 12, 36);
-  if (u[0] != 0 || u[8] != 2 || u[7] != 1 || u[6] != 1 || !u[2] || !u[3] || u[2] > 16384 || u[3] > 16384) return -2;      // scheme 2 = Zstandard; 1 level, 1 face
-  uint64_t lu; memcpy(&lo, b + 80, 8); memcpy(&ll, b + 88, 8); memcpy(&lu, b + 96, 8);
-  layers = u[5] ? u[5] : 1; w = u[2]; h = u[3];
-  if (layers > 64) return -4;
-  need = (uint64_t)layers * ((u[2] + 3) / 4) * ((u[3] + 3) / 4) * 16;
-  if (lo < 104 || lo > n || ll > n - lo || lu != need) return -4;
+  if (u[0] != 0 || u[8] != 2 || u[7] < 1 || u[6] != 1 || !u[2] || !u[3] || u[2] > 16384 || u[3] > 16384) return -2;      // scheme 2 = Zstandard; 1 face
+  Z.layers = u[5] ? u[5] : 1; Z.w = u[2]; Z.h = u[3]; Z.levels = u[7];
+  if (Z.layers > 64) return -4;
+  if ((int)Z.levels > mip_level_count(Z.w, Z.h) || (uint64_t)80 + 24ull * Z.levels > n) return -4;
+  Z.head = n;                                              // everything ahead of the first level's data: header, index, DFD, key-values
+  for (uint32_t v = 0; v < Z.levels; v++) {
+    uint64_t lu; memcpy(&Z.lo[v], b + 80 + 24 * v, 8); memcpy(&Z.ll[v], b + 88 + 24 * v, 8); memcpy(&lu, b + 96 + 24 * v, 8);
+    const uint32_t lw = std::max(1u, Z.w >> v), lh = std::max(1u, Z.h >> v);
+    Z.need[v] = (uint64_t)Z.layers * ((lw + 3) / 4) * ((lh + 3) / 4) * 16;
+    if (Z.lo[v] < 80 + 24ull * Z.levels || Z.lo[v] > n || Z.ll[v] > n - Z.lo[v] || lu != Z.need[v]) return -4;
+    Z.head = std::min(Z.head, Z.lo[v]);
+  }
   return 0;
 }
 // width / height / layers of a Zstandard-supercompressed UASTC file from its header alone (uvol_ktx2_info: nothing is inflated to report a size)
-int uastc_zstd_info(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L) {
-  uint32_t w, h, l; uint64_t lo, ll, need;
-  const int r = uastc_zstd_header(b, n, w, h, l, lo, ll, need); if (r) return r;
-  *W = w; *H = h; *L = l; return 0;
+int uastc_zstd_info(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint32_t *levels) {
+  UZstdHead Z;
+  const int r = uastc_zstd_header(b, n, Z); if (r) return r;
+  *W = Z.w; *H = Z.h; *L = Z.layers; if (levels) *levels = Z.levels; return 0;
 }
 int uastc_unzstd(const uint8_t *b, size_t n, std::vector<uint8_t> &out) {
   typedef size_t (*dec_fn)(void *, size_t, const void *, size_t); typedef unsigned (*err_fn)(size_t); typedef unsigned long long (*fcs_fn)(const void *, size_t);
@@ -720,20 +753,30 @@ int uastc_unzstd(const uint8_t *b, size_t n, std::vector<uint8_t> &out) {
   static const bool have = [] {
     void *h = dlopen("libzstd.so.1", RTLD_NOW | RTLD_LOCAL); if (!h) h = dlopen("libzstd.so", RTLD_NOW | RTLD_LOCAL); if (!h) return false;
     dec = (dec_fn)dlsym(h, "ZSTD_decompress"); is_err = (err_fn)dlsym(h, "ZSTD_isError"); fcs = (fcs_fn)dlsym(h, "ZSTD_getFrameContentSize"); return dec && is_err && fcs; }();
-  uint32_t w, h, layers; uint64_t lo, ll, need;
-  const int rh = uastc_zstd_header(b, n, w, h, layers, lo, ll, need); if (rh) return rh;
+  UZstdHead Z;
+  const int rh = uastc_zstd_header(b, n, Z); if (rh) return rh;
   if (!have) return 1;
   // `need` comes from header fields a crafted 150-byte file controls (up to 64 layers x 16384^2 texels = 17 GB): nothing is allocated before
-  // the FRAME says the same size (one-shot ZSTD_compress, which basisu uses, records it), and never more than a Zstandard frame of `ll` bytes can hold
-  const unsigned long long fsz = fcs(b + lo, (size_t)ll);
-  if (fsz != need || need > (uint64_t)ll * 65536ull + 65536ull) return -5;
-  const size_t head = (size_t)lo, off = (head + 15) & ~(size_t)15;
-  try { out.assign(off + (size_t)need, 0); } catch (...) { out.clear(); return -6; }
+  // every level's FRAME says the same size (one-shot ZSTD_compress, which basisu uses, records it), and never more than a Zstandard frame of `ll` bytes can hold
+  uint64_t total = 0;
+  for (uint32_t v = 0; v < Z.levels; v++) {
+    const unsigned long long fsz = fcs(b + Z.lo[v], (size_t)Z.ll[v]);
+    if (fsz != Z.need[v] || Z.need[v] > (uint64_t)Z.ll[v] * 65536ull + 65536ull) return -5;
+    total += Z.need[v];
+  }
+  // the equivalent scheme-0 file: the same head, the levels smallest first from a 16-byte aligned offset on
+  const size_t head = (size_t)Z.head, off = (head + 15) & ~(size_t)15;
+  try { out.assign(off + (size_t)total, 0); } catch (...) { out.clear(); return -6; }
   memcpy(out.data(), b, head);
-  const size_t got = dec(out.data() + off, (size_t)need, b + lo, (size_t)ll);
-  if (is_err(got) || got != need) return -5;
-  const uint32_t scheme0 = 0; const uint64_t off64 = off;
-  memcpy(out.data() + 12 + 32, &scheme0, 4); memcpy(out.data() + 80, &off64, 8); memcpy(out.data() + 88, &need, 8); memcpy(out.data() + 96, &need, 8);
+  uint64_t at = off;
+  for (int v = (int)Z.levels - 1; v >= 0; v--) {
+    const size_t got = dec(out.data() + at, (size_t)Z.need[v], b + Z.lo[v], (size_t)Z.ll[v]);
+    if (is_err(got) || got != Z.need[v]) return -5;
+    memcpy(out.data() + 80 + 24 * v, &at, 8); memcpy(out.data() + 88 + 24 * v, &Z.need[v], 8); memcpy(out.data() + 96 + 24 * v, &Z.need[v], 8);
+    at += Z.need[v];
+  }
+  const uint32_t scheme0 = 0;
+  memcpy(out.data() + 12 + 32, &scheme0, 4);
   return 0;
 }
 
@@ -782,14 +825,87 @@ int tex_uastc_encode_segments(uvol_ctx *ctx, const uint8_t *const *rgba, int n_s
   return status ? UVOL_OK : worst;
 }
 
+// The same with mip levels inside each file (uvol_encode_texture_segments_mips): level 0 from the caller's layers as above, levels
+// 1 .. levels - 1 from the chain kernel (tex_mipchain.hip) on the context's stream, then one k_uastc_encode launch per level - a level is a
+// UastcJob with its own W, H, bx, by, and y_flip applies to the level's own height.  The blocks of a segment lie in file order (smallest
+// level first), so that a segment is one copy behind its header.  levels: resolved (>= 2) and checked by the caller (mip_check).
+size_t uastc_mips_bound(uint32_t W, uint32_t H, int n_layers, int levels) {
+  uint64_t len[UVOL_MIP_MAX_LEVELS];
+  for (int v = 0; v < levels; v++) { const uint32_t lw = std::max(1u, W >> v), lh = std::max(1u, H >> v); len[v] = (uint64_t)n_layers * ((lw + 3) / 4) * ((lh + 3) / 4) * 16; }
+  return uastc_header(nullptr, W, H, (uint32_t)n_layers, false, levels, len, nullptr);
+}
+int tex_uastc_encode_segments_mips(uvol_ctx *ctx, const uint8_t *const *rgba, int n_seg, int n_layers, uint32_t W, uint32_t H,
+                                   bool on_device, int levels, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
+  static const char who[] = "uvol_encode_texture_segments_mips";
+  UastcState *U = ctx->uastc;
+  if (n_seg <= 0) return UVOL_OK;
+  if (n_layers > 64 || n_seg > 65535 || levels < 2 || levels > UVOL_MIP_MAX_LEVELS) { ctx->set_error("texture segment: unsupported size"); return UVOL_E_UNSUPPORTED; }
+  int rc; if ((rc = uastc_consts(ctx))) return rc;
+  const int NL = n_seg * n_layers;
+  const size_t lbytes = (size_t)W * H * 4;
+  uint32_t lw[UVOL_MIP_MAX_LEVELS], lh[UVOL_MIP_MAX_LEVELS]; uint64_t llen[UVOL_MIP_MAX_LEVELS], loff[UVOL_MIP_MAX_LEVELS];
+  for (int v = 0; v < levels; v++) { lw[v] = std::max(1u, W >> v); lh[v] = std::max(1u, H >> v); llen[v] = (uint64_t)n_layers * ((lw[v] + 3) / 4) * ((lh[v] + 3) / 4) * 16; }
+  const size_t file_len = uastc_header(nullptr, W, H, (uint32_t)n_layers, false, levels, llen, loff);
+  const size_t data_off = (size_t)loff[levels - 1], seg_bytes = file_len - data_off;
+  // level 0 on the device
+  std::vector<const uint8_t *> l0(rgba, rgba + NL);
+  if (!on_device) {
+    if ((rc = uvol_ensure(ctx, U->layers, lbytes * (size_t)NL))) return rc;
+    std::vector<UvolUpItem> ups; ups.reserve((size_t)NL);
+    for (int i = 0; i < NL; i++) { ups.push_back(UvolUpItem{ lbytes * (size_t)i, rgba[i], lbytes }); l0[(size_t)i] = (const uint8_t *)U->layers.p + lbytes * (size_t)i; }
+    if ((rc = uvol_upload_staged(ctx, (uint8_t *)U->layers.p, ups))) return rc;
+  }
+  // levels 1 .. : the chain, in the slot kept for this entry point (device inputs are ordered behind their un-filter there)
+  std::vector<const uint8_t *> chain((size_t)NL * (levels - 1), nullptr);
+  if ((rc = mip_rgba_batch(ctx, who, l0.data(), NL, W, H, true, levels, 2, chain.data(), false))) return rc;
+  if ((rc = uvol_ensure(ctx, U->jobs, sizeof(UastcJob) * (size_t)n_seg * levels))) return rc;
+  if ((rc = uvol_ensure(ctx, U->blocks, seg_bytes * (size_t)n_seg))) return rc;
+  U->hjobs.assign((size_t)n_seg * levels, UastcJob{});
+  for (int v = 0; v < levels; v++) for (int s = 0; s < n_seg; s++) {
+    UastcJob &J = U->hjobs[(size_t)v * n_seg + s];
+    J.W = lw[v]; J.H = lh[v]; J.L = (uint32_t)n_layers; J.bx = (lw[v] + 3) / 4; J.by = (lh[v] + 3) / 4; J.yflip = ctx->prm.y_flip ? 1 : 0;
+    const size_t nb = (size_t)J.bx * J.by;
+    for (int l = 0; l < n_layers; l++) {
+      const size_t i = (size_t)s * n_layers + l;
+      J.layer[l] = v == 0 ? l0[i] : chain[i * (levels - 1) + (v - 1)];
+      J.out[l] = (uint8_t *)U->blocks.p + seg_bytes * (size_t)s + (size_t)(loff[v] - data_off) + nb * 16 * (size_t)l;
+    }
+  }
+  UVOL_HIP_CHECK(ctx, hipMemcpyAsync(U->jobs.p, U->hjobs.data(), sizeof(UastcJob) * U->hjobs.size(), hipMemcpyHostToDevice, ctx->stream));
+  { uvol_ctx::Scope sc(ctx, "tex.uastc_encode_mips", (uint64_t)(lbytes * 4 / 3 + seg_bytes / n_layers) * n_layers * (uint64_t)n_seg);
+    for (int v = 0; v < levels; v++) {
+      const size_t nb = (size_t)((lw[v] + 3) / 4) * ((lh[v] + 3) / 4);
+      hipLaunchKernelGGL(k_uastc_encode, dim3(uvol_blocks(nb), (unsigned)n_layers, (unsigned)n_seg), dim3(UVOL_BLOCK), 0, ctx->stream, (UastcJob *)U->jobs.p + (size_t)v * n_seg, (const UConst *)U->consts.p);
+      UVOL_HIP_CHECK(ctx, hipGetLastError());
+    } }
+  if ((rc = uastc_pinned(ctx, seg_bytes * (size_t)n_seg))) return rc;
+  UVOL_HIP_CHECK(ctx, hipMemcpyAsync(U->hjobs.data(), U->jobs.p, sizeof(UastcJob) * U->hjobs.size(), hipMemcpyDeviceToHost, ctx->stream));
+  UVOL_HIP_CHECK(ctx, hipMemcpyAsync(U->pinned, U->blocks.p, seg_bytes * (size_t)n_seg, hipMemcpyDeviceToHost, ctx->stream));
+  UVOL_HIP_CHECK(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->resolve_profile();
+  int worst = UVOL_OK;
+  for (int s = 0; s < n_seg; s++) {
+    out_lens[s] = file_len;
+    if (status) status[s] = UVOL_OK;
+    if (out_lens[s] > caps[s]) { ctx->set_error("texture segment %d: output buffer too small (%zu > %zu)", s, out_lens[s], caps[s]); worst = UVOL_E_NOSPACE; if (status) status[s] = UVOL_E_NOSPACE; continue; }
+    bool alpha = false; for (int v = 0; v < levels; v++) alpha = alpha || U->hjobs[(size_t)v * n_seg + s].any_alpha != 0;      // the channel id says RGBA when any level has a block with alpha
+    (void)uastc_header(outs[s], W, H, (uint32_t)n_layers, alpha, levels, llen, nullptr);
+    memcpy(outs[s] + data_off, U->pinned + seg_bytes * (size_t)s, seg_bytes);
+  }
+  return status ? UVOL_OK : worst;
+}
+
 // UASTC .ktx2 files -> target 0: RGBA8 layers, target 3: ASTC 4x4 blocks (layer buffers of the caller, host or device)
-int tex_uastc_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uint8_t *const *outp, size_t layer_cap, bool outputs_on_device, int target, int *status) {
+// level: which mip level of every file (its blocks and its own dimensions; the caller has checked that every file has it)
+int tex_uastc_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uint8_t *const *outp, size_t layer_cap, bool outputs_on_device, int target, int *status, int level) {
   UastcState *U = ctx->uastc;
   if (n <= 0) return UVOL_OK;
   if (target < 0 || target > 6) { ctx->set_error("unknown transcode target %d", target); return UVOL_E_UNSUPPORTED; }
   int rc; if ((rc = uastc_consts(ctx))) return rc;
-  uint32_t W = 0, H = 0, L = 0; uint64_t lo = 0;
-  if (uastc_ktx2_probe(files[0], lens[0], &W, &H, &L, &lo)) { ctx->set_error("segment 0: not a UASTC .ktx2 this decoder handles"); return UVOL_E_INVALID; }
+  uint32_t W = 0, H = 0, L = 0, NV = 0; uint64_t lo[UVOL_MIP_MAX_LEVELS];
+  if (level < 0 || uastc_ktx2_probe_levels(files[0], lens[0], &W, &H, &L, &NV, lo) || (uint32_t)level >= NV) { ctx->set_error("segment 0: not a UASTC .ktx2 this decoder handles (or without level %d)", level); return UVOL_E_INVALID; }
+  const uint32_t W0 = W, H0 = H;
+  W = std::max(1u, W0 >> level); H = std::max(1u, H0 >> level);
   const uint32_t bx = (W + 3) / 4, by = (H + 3) / 4; const size_t nb = (size_t)bx * by, seg_bytes = nb * 16 * (size_t)L;
   const size_t layer_bytes = target == 0 ? (size_t)W * H * 4 : ((target == 5 || target == 1) ? nb * 8 : nb * 16);
   if (layer_cap < layer_bytes) { ctx->set_error("layer buffers too small (%zu < %zu)", layer_cap, layer_bytes); return UVOL_E_NOSPACE; }
@@ -798,9 +914,9 @@ int tex_uastc_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const 
   if (!outputs_on_device && (rc = uvol_ensure(ctx, U->outs, layer_bytes * (size_t)L * (size_t)n))) return rc;
   U->hjobs.assign((size_t)n, UastcJob{});
   for (int s = 0; s < n; s++) {
-    uint32_t w2, h2, l2; uint64_t lo2;
-    if (uastc_ktx2_probe(files[s], lens[s], &w2, &h2, &l2, &lo2) || w2 != W || h2 != H || l2 != L) { ctx->set_error("segment %d: not a UASTC .ktx2 of the batch's size", s); return UVOL_E_INVALID; }
-    UVOL_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)U->blocks.p + seg_bytes * (size_t)s, files[s] + lo2, seg_bytes, hipMemcpyHostToDevice, ctx->stream));
+    uint32_t w2, h2, l2, nv2; uint64_t lo2[UVOL_MIP_MAX_LEVELS];
+    if (uastc_ktx2_probe_levels(files[s], lens[s], &w2, &h2, &l2, &nv2, lo2) || w2 != W0 || h2 != H0 || l2 != L || (uint32_t)level >= nv2) { ctx->set_error("segment %d: not a UASTC .ktx2 of the batch's size", s); return UVOL_E_INVALID; }
+    UVOL_HIP_CHECK(ctx, hipMemcpyAsync((uint8_t *)U->blocks.p + seg_bytes * (size_t)s, files[s] + lo2[level], seg_bytes, hipMemcpyHostToDevice, ctx->stream));
     UastcJob &J = U->hjobs[s]; J.W = W; J.H = H; J.L = L; J.bx = bx; J.by = by;
     for (uint32_t l = 0; l < L; l++) {
       J.layer[l] = (const uint8_t *)U->blocks.p + seg_bytes * (size_t)s + nb * 16 * (size_t)l;

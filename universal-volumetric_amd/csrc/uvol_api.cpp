@@ -269,7 +269,7 @@ void uvol_ctx_destroy(uvol_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   ctx->resolve_profile();
   geo_destroy(ctx); tex_destroy(ctx); uvol_uplink_destroy(ctx);      // (the lanes' streams are synchronised and gone before the slots they read are freed)
-  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx); down_destroy(ctx); etc2_destroy(ctx);
+  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx); down_destroy(ctx); mip_destroy(ctx); etc2_destroy(ctx);
   for (int k = 0; k < 2; k++) { if (ctx->up_pin[k]) (void)hipHostFree(ctx->up_pin[k]); if (ctx->up_ev[k]) (void)hipEventDestroy(ctx->up_ev[k]); }
   for (int k = 0; k < 2; k++) if (ctx->pin_ev[k]) (void)hipEventDestroy(ctx->pin_ev[k]);
   for (int k = 0; k < 2; k++) { if (ctx->dn_pin[k]) (void)hipHostFree(ctx->dn_pin[k]); if (ctx->dn_ev[k]) (void)hipEventDestroy(ctx->dn_ev[k]); }
@@ -302,6 +302,7 @@ int uvol_trim(uvol_ctx *ctx) {
   const int ru = tex_trim(ctx); if (rt == UVOL_OK) rt = ru;
   uvol_uplink_trim(ctx);
   down_trim(ctx);
+  mip_trim(ctx);
   etc2_trim(ctx);
   return rc != UVOL_OK ? rc : (rf != UVOL_OK ? rf : (rx != UVOL_OK ? rx : rt));
 }
@@ -539,10 +540,12 @@ static int decode_dispatch(uvol_ctx *ctx, const uint8_t *const *ktx2_in, const s
 // first readable file fixes the batch's width / height / layer count and a file of another shape is UVOL_E_INVALID in its slot; a source
 // kind that does not transcode to the target is UVOL_E_UNSUPPORTED in its slot; ETC1S and UASTC files run as one batch per kind; a file
 // whose payload turns out corrupt on the device fails alone.  The call itself fails only for bad arguments, memory or the device.
-int uvol_transcode_texture_segments_st(uvol_ctx *ctx, const uint8_t *const *ktx2_in, const size_t *lens_in, int n_segments,
-                                       uint8_t *const *out, size_t layer_cap, int outputs_on_device, int target, int *status) {
+// level: the mip level every file is asked for (uvol_transcode_texture_segments_level); a file without it - a UASTC file with fewer levels, an
+// ETC1S file for any level but 0 - is UVOL_E_INVALID in its slot; the batch's shape stays the files' level-0 width / height / layer count
+static int transcode_st_common(uvol_ctx *ctx, const uint8_t *const *ktx2_in, const size_t *lens_in, int n_segments,
+                               uint8_t *const *out, size_t layer_cap, int outputs_on_device, int target, int *status, int level) {
   UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2_in || !lens_in || n_segments <= 0 || !out || !status || target < UVOL_TARGET_RGBA32 || target > UVOL_TARGET_BC3) return UVOL_E_INVALID;
+  if (!ctx || !ktx2_in || !lens_in || n_segments <= 0 || !out || !status || target < UVOL_TARGET_RGBA32 || target > UVOL_TARGET_BC3 || level < 0) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
   const int n = n_segments;
   const UvolUnzstd Z(ktx2_in, lens_in, n);                  // (Zstandard-supercompressed UASTC files: inflated on the host, see decode_dispatch)
@@ -552,12 +555,13 @@ int uvol_transcode_texture_segments_st(uvol_ctx *ctx, const uint8_t *const *ktx2
   for (int i = 0; i < n; i++) {
     status[i] = UVOL_E_INVALID;
     if (!ktx2[i]) continue;
-    uint32_t w = 0, h = 0, l = 0; uint64_t lo = 0;
-    const int pu = uastc_ktx2_probe(ktx2[i], lens[i], &w, &h, &l, &lo);
+    uint32_t w = 0, h = 0, l = 0, nv = 1;
+    const int pu = uastc_ktx2_probe_levels(ktx2[i], lens[i], &w, &h, &l, &nv, nullptr);
     if (pu == UASTC_PROBE_SUPERCOMPRESSED) { status[i] = UVOL_E_UNSUPPORTED; continue; }
     int k = -1;
     if (pu == 0) k = 1;
-    else { const int ri = uvol_ktx2_info(ktx2[i], lens[i], &w, &h, &l); if (ri != UVOL_OK) { status[i] = ri; continue; } k = 0; }
+    else { const int ri = uvol_ktx2_info(ktx2[i], lens[i], &w, &h, &l); if (ri != UVOL_OK) { status[i] = ri; continue; } k = 0; nv = 1; }
+    if ((uint32_t)level >= nv) continue;                                     // the file has no such level: UVOL_E_INVALID
     if (!have) { W0 = w; H0 = h; L0 = l; have = true; }
     else if (w != W0 || h != H0 || l != L0) continue;                       // another shape than the batch's: UVOL_E_INVALID
     if (k == 0 && target == UVOL_TARGET_ASTC) { status[i] = UVOL_E_UNSUPPORTED; continue; }      // (ASTC is the target of UASTC sources only; UASTC sources take every target)
@@ -574,11 +578,65 @@ int uvol_transcode_texture_segments_st(uvol_ctx *ctx, const uint8_t *const *ktx2
     if (ix.empty()) continue;
     std::vector<const uint8_t *> f(ix.size()); std::vector<size_t> ln(ix.size()); std::vector<uint8_t *> o(ix.size() * L0); std::vector<int> st(ix.size(), UVOL_OK);
     for (size_t j = 0; j < ix.size(); j++) { f[j] = ktx2[ix[j]]; ln[j] = lens[ix[j]]; for (uint32_t l = 0; l < L0; l++) o[j * L0 + l] = out[(size_t)ix[j] * L0 + l]; }
-    const int rc = k == 1 ? tex_uastc_decode_segments(ctx, f.data(), ln.data(), (int)ix.size(), o.data(), layer_cap, outputs_on_device != 0, target, st.data())
+    const int rc = k == 1 ? tex_uastc_decode_segments(ctx, f.data(), ln.data(), (int)ix.size(), o.data(), layer_cap, outputs_on_device != 0, target, st.data(), level)
                           : tex_decode_segments(ctx, f.data(), ln.data(), (int)ix.size(), o.data(), layer_cap, outputs_on_device != 0, target, st.data());
     if (rc == UVOL_E_HIP || rc == UVOL_E_NOSPACE) return rc;                 // the device / the caller's layer buffers: the call's failure
     for (size_t j = 0; j < ix.size(); j++) status[ix[j]] = rc != UVOL_OK ? rc : st[j];
   }
+  return UVOL_OK;
+}
+int uvol_transcode_texture_segments_st(uvol_ctx *ctx, const uint8_t *const *ktx2_in, const size_t *lens_in, int n_segments,
+                                       uint8_t *const *out, size_t layer_cap, int outputs_on_device, int target, int *status) {
+  return transcode_st_common(ctx, ktx2_in, lens_in, n_segments, out, layer_cap, outputs_on_device, target, status, 0);
+}
+int uvol_transcode_texture_segments_level(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, int level,
+                                          uint8_t *const *outs, size_t layer_cap, int target, int outputs_on_device, int *status) {
+  if (ctx && level < 0) { ctx->set_error("uvol_transcode_texture_segments_level: level %d", level); return UVOL_E_INVALID; }
+  return transcode_st_common(ctx, ktx2, lens, n_segments, outs, layer_cap, outputs_on_device, target, status, level);
+}
+// ---- mip levels ----
+int uvol_mip_level_count(uint32_t width, uint32_t height) { return mip_level_count(width, height); }
+int uvol_mipchain_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height, int inputs_on_device, int levels, int slot, const uint8_t **rgba_dev_out) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx) return UVOL_E_INVALID;
+  if (n <= 0) return UVOL_OK;
+  if (!rgba || !rgba_dev_out) { ctx->set_error("uvol_mipchain_rgba_batch_dev: %s is NULL", !rgba ? "rgba" : "rgba_dev_out"); return UVOL_E_INVALID; }
+  if (slot < 0 || slot > 1) { ctx->set_error("uvol_mipchain_rgba_batch_dev: slot %d (0 or 1)", slot); return UVOL_E_INVALID; }
+  (void)hipSetDevice(ctx->device);
+  return mip_rgba_batch(ctx, "uvol_mipchain_rgba_batch_dev", rgba, n, width, height, inputs_on_device != 0, levels, slot, rgba_dev_out, true);
+}
+size_t uvol_texture_bound_mips(uint32_t width, uint32_t height, int n_layers, int levels) {
+  if (!width || !height || n_layers <= 0 || levels < 0 || levels > mip_level_count(width, height)) return 0;
+  const int nl = levels ? levels : mip_level_count(width, height);
+  return std::max(uvol_texture_bound(width, height, n_layers), uastc_mips_bound(width, height, n_layers, nl));      // (levels == 1 goes through uvol_encode_texture_segments_st)
+}
+int uvol_encode_texture_segments_mips(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height,
+                                      int inputs_on_device, int levels, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx || !rgba || n_segments <= 0 || n_layers < 1 || !outs || !caps || !out_lens || !status) return UVOL_E_INVALID;
+  (void)hipSetDevice(ctx->device);
+  if (!ctx->prm.uastc && levels != 1) { ctx->set_error("mip levels are written in the UASTC mode only (DESIGN.md section 7)"); return UVOL_E_UNSUPPORTED; }
+  for (int s = 0; s < n_segments; s++) { status[s] = UVOL_OK; out_lens[s] = 0; }
+  int nl = 1;
+  if (levels != 1) {
+    if (int rc = mip_check(ctx, "uvol_encode_texture_segments_mips", width, height, levels, &nl)) return rc;
+    for (int i = 0; i < n_segments * n_layers; i++) {
+      if (!rgba[i]) { ctx->set_error("uvol_encode_texture_segments_mips: rgba[%d] is NULL", i); return UVOL_E_INVALID; }
+      if (inputs_on_device && ((uintptr_t)rgba[i] & 3)) { ctx->set_error("uvol_encode_texture_segments_mips: rgba[%d] is a device layer that is not 4-byte aligned", i); return UVOL_E_INVALID; }
+    }
+  }
+  if (nl == 1) {
+    if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
+    return tex_encode_segments(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
+  }
+  return tex_uastc_encode_segments_mips(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, nl, outs, caps, out_lens, status);
+}
+int uvol_ktx2_levels(const uint8_t *ktx2, size_t len, uint32_t *levels) {
+  uint32_t w, h, l, nv = 0;
+  const int pr = uastc_ktx2_probe_levels(ktx2, len, &w, &h, &l, &nv, nullptr);
+  if (pr == UASTC_PROBE_SUPERCOMPRESSED) { if (uastc_zstd_info(ktx2, len, &w, &h, &l, &nv) != 0) return UVOL_E_UNSUPPORTED; }
+  else if (pr != 0) { const int ri = uvol_ktx2_info(ktx2, len, &w, &h, &l); if (ri != UVOL_OK) return ri; nv = 1; }      // an ETC1S file this decoder reads has one level
+  if (levels) *levels = nv;
   return UVOL_OK;
 }
 int uvol_encode_texture_segments_st(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height,

@@ -159,6 +159,7 @@ struct ObjState;     // OBJ text ingest on the device (obj_ingest.hip)
 struct PngState;     // PNG scanlines un-filtered on the device (png_ingest.hip)
 struct DownState;    // RGBA layers downscaled on the device (tex_downscale.hip)
 struct Etc2State;    // RGBA layers encoded to full ETC1 blocks (tex_etc2.hip)
+struct MipState;     // mip chains of RGBA layers made on the device (tex_mipchain.hip)
 
 struct uvol_ctx {
   int device = 0;
@@ -178,6 +179,7 @@ struct uvol_ctx {
   PngState *png = nullptr;
   DownState *down = nullptr;      // created by the first uvol_downscale_rgba_batch_dev
   Etc2State *etc2 = nullptr;      // created by the first uvol_encode_etc2_rgb_batch
+  MipState *mip = nullptr;        // created by the first uvol_mipchain_rgba_batch_dev / uvol_encode_texture_segments_mips
   // enqueue form of the ABI (uvol_*_async + uvol_sync): calls run in order on this context's worker thread
   struct AsyncQ {
     std::mutex m; std::condition_variable cv_work, cv_idle; std::deque<std::function<int()>> q; std::thread th; bool busy = false, stop = false; int first_err = 0; char err[512] = {0};
@@ -273,6 +275,17 @@ int png_status(uvol_ctx *ctx, int slot, int *status, int n);
 int down_rgba_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
 void down_trim(uvol_ctx *ctx);
 void down_destroy(uvol_ctx *ctx);
+#define DOWN_BUCKETS 4096                               /* m >> 4, m <= 65535 */
+#define DOWN_TABLE_WORDS (512 + DOWN_BUCKETS / 4)
+bool down_tables(uint32_t *t);      // lin[256], mid[256], base[DOWN_BUCKETS] of the filter (tex_downscale.hip); false: the bucket search disagrees with the plain one
+// uvol_mipchain_rgba_batch_dev (tex_mipchain.hip); the state is created by the first call.  slot 0 / 1: the caller's chain slots, 2: the one
+// uvol_encode_texture_segments_mips keeps for itself; wait: synchronise the context's stream before returning
+#define UVOL_MIP_MAX_LEVELS 15
+int mip_level_count(uint32_t w, uint32_t h);
+int mip_check(uvol_ctx *ctx, const char *who, uint32_t w, uint32_t h, int levels, int *levels_out);
+int mip_rgba_batch(uvol_ctx *ctx, const char *who, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, int levels, int slot, const uint8_t **rgba_dev_out, bool wait);
+void mip_trim(uvol_ctx *ctx);
+void mip_destroy(uvol_ctx *ctx);
 // uvol_encode_etc2_rgb_batch (tex_etc2.hip); the state is created by the first call
 int etc2_rgb_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, uint8_t *const *blocks, size_t layer_cap, bool outputs_on_device);
 void etc2_trim(uvol_ctx *ctx);
@@ -281,7 +294,8 @@ int uastc_create(uvol_ctx *ctx);
 void uastc_destroy(uvol_ctx *ctx);
 #define UASTC_PROBE_SUPERCOMPRESSED (-10)      /* a UASTC .ktx2 (DFD colour model 166) whose level data are Zstandard-supercompressed */
 int uastc_ktx2_probe(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint64_t *lvl_off);
-int uastc_zstd_info(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L);      // sizes of a Zstandard-supercompressed UASTC file from its header (nothing inflated)
+int uastc_ktx2_probe_levels(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint32_t *levels, uint64_t *lvl_offs);      // every level of the index checked; lvl_offs: UVOL_MIP_MAX_LEVELS entries or nullptr
+int uastc_zstd_info(const uint8_t *b, size_t n, uint32_t *W, uint32_t *H, uint32_t *L, uint32_t *levels = nullptr);      // sizes of a Zstandard-supercompressed UASTC file from its header (nothing inflated)
 int tdec_file_alpha(const uint8_t *b, size_t n);          // ETC1S .ktx2: 1 = has alpha slices, 0 = opaque, < 0 = not a file the ETC1S decoder reads (tex_decode.hip)
 int uastc_unzstd(const uint8_t *b, size_t n, std::vector<uint8_t> &out);      // Zstandard-supercompressed UASTC -> the equivalent scheme-0 file (needs the system's libzstd; tex_uastc.hip)
 // the files of a decode / transcode call with every Zstandard-supercompressed UASTC file replaced by its inflated equivalent (kept alive here)
@@ -299,7 +313,10 @@ struct UvolUnzstd {
 };
 int tex_uastc_encode_segments(uvol_ctx *ctx, const uint8_t *const *rgba, int n_seg, int n_layers, uint32_t w, uint32_t h,
                               bool inputs_on_device, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status = nullptr);
-int tex_uastc_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uint8_t *const *out, size_t layer_cap, bool outputs_on_device, int target, int *status = nullptr);
+int tex_uastc_decode_segments(uvol_ctx *ctx, const uint8_t *const *files, const size_t *lens, int n, uint8_t *const *out, size_t layer_cap, bool outputs_on_device, int target, int *status = nullptr, int level = 0);
+size_t uastc_mips_bound(uint32_t w, uint32_t h, int n_layers, int levels);
+int tex_uastc_encode_segments_mips(uvol_ctx *ctx, const uint8_t *const *rgba, int n_seg, int n_layers, uint32_t w, uint32_t h,
+                                   bool inputs_on_device, int levels, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status);
 int tex_create(uvol_ctx *ctx);
 void tex_destroy(uvol_ctx *ctx);
 int tex_encode_segments(uvol_ctx *ctx, const uint8_t *const *rgba, int n_seg, int n_layers, uint32_t w, uint32_t h,

@@ -4,7 +4,7 @@
 // player reads (src/Interfaces.ts:75-132, src/V2/player.ts:141-174).
 //
 //   uvolenc project-config.json [--gpus N] [--device D] [--batch-frames F] [--ingest-threads T] [--targets ktx2[,etc2]] [--uastc] [--material-seams] [--device-inflate [--tex-batch-frames F]]
-//                               [--texture-ladder F[,F...] [--etc2-scale F]] [--etc2-direct] [--force] [--encoder-py-manifest]
+//                               [--texture-ladder F[,F...] [--etc2-scale F]] [--etc2-direct] [--mipmaps [N]] [--force] [--encoder-py-manifest]
 //   --targets   texture targets to write (src/Interfaces.ts:19 TextureFileFormat): `ktx2` always; `etc2` adds one raw ETC2 RGB
 //               (ETC1-subset) block image per frame, transcoded on the GPU from the ETC1S segments, and a second target in the manifest
 //   --texture-ladder   reduced-resolution tiers (src/Interfaces.ts:41-73: every texture target has its own `resolution`): for every factor F of
@@ -16,6 +16,9 @@
 //   --etc2-direct   the raw `etc2` target is ENCODED from the batch's layers in HBM (with --etc2-scale F: from that rung's downscaled layers) by a
 //               search over all of ETC1 (uvol_encode_etc2_rgb_batch) instead of transcoded from the segments: same file names, sizes and manifest,
 //               better blocks; the target is then independent of the segment encoder, so it may be combined with --uastc
+//   --mipmaps [N]   with --uastc: every .ktx2 - the ktx2 target and every --texture-ladder rung - carries N mip levels (default, or N = 0: the full
+//               chain; N beyond a size's chain is its full chain), made on the GPU (uvol_encode_texture_segments_mips).  A level must divide the
+//               size exactly (include/uvol_codec.h); file names and uvol.json do not change
 //   --uastc     the KTX2 files carry UASTC LDR 4x4 blocks (`basisu -uastc`) instead of ETC1S/BasisLZ
 //   --material-seams   (or UVOL_MATERIAL_SEAMS=1) frames whose `usemtl` materials meet at shared vertices are written with the material
 //               attribute as a corner attribute instead of without it
@@ -71,6 +74,7 @@ int main(int argc, char **argv) {
   { const char *e = std::getenv("UVOL_TIMING"); g_timing = e && *e == '1'; }
   int n_gpus = 1, device0 = 0, frames_per_batch = 32, ingest_threads = 0; bool force = false, encpy = false, want_etc2 = false, uastc = false, host_obj = false, host_png = false, dev_inflate = false, pinned_text = false, material_seams = false, etc2_direct = false; int tex_batch_frames = 0;
   std::vector<int> ladder; int etc2_scale = 1;      // --texture-ladder: the rungs' factors in the order given; --etc2-scale
+  int mipmaps = -1;                                  // --mipmaps [N]: -1 off, 0 the full chain, N levels
   { const char *e = std::getenv("UVOL_MATERIAL_SEAMS"); material_seams = e && *e == '1'; }      // (= --material-seams)
   for (int i = 2; i < argc; i++) {
     if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) n_gpus = std::atoi(argv[++i]);
@@ -84,6 +88,10 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--tex-batch-frames") && i + 1 < argc) tex_batch_frames = std::atoi(argv[++i]);      // images per texture call (default: --batch-frames)
     else if (!std::strcmp(argv[i], "--host-obj-parser")) host_obj = true;          // OBJ text parsed by the ingest threads (as until round 3) instead of on the GPU
     else if (!std::strcmp(argv[i], "--uastc")) uastc = true;
+    else if (!std::strcmp(argv[i], "--mipmaps")) {
+      mipmaps = 0;
+      if (i + 1 < argc && argv[i + 1][0] >= '0' && argv[i + 1][0] <= '9') { mipmaps = std::atoi(argv[++i]); if (mipmaps > 15) { std::printf("❌ --mipmaps takes 0 (the full chain) .. 15 levels\n"); return 1; } }
+    }
     else if (!std::strcmp(argv[i], "--material-seams")) material_seams = true;      // frames whose materials meet at shared vertices keep their material attribute (uvol_params.material_seams)
     else if (!std::strcmp(argv[i], "--encoder-py-manifest")) encpy = true;
     else if (!std::strcmp(argv[i], "--etc2-direct")) etc2_direct = true;
@@ -109,6 +117,7 @@ int main(int argc, char **argv) {
     }
   }
   if (want_etc2 && uastc && !etc2_direct) { std::printf("❌ the etc2 target is transcoded from ETC1S segments; it cannot be combined with --uastc\n"); return 1; }
+  if (mipmaps >= 0 && !uastc) { std::printf("❌ --mipmaps needs --uastc: mip levels are written in the UASTC mode only (DESIGN.md section 7)\n"); return 1; }
   if (etc2_direct && !want_etc2) { std::printf("❌ --etc2-direct needs --targets etc2 (it chooses how that target is made)\n"); return 1; }
   if (etc2_scale != 1 && std::find(ladder.begin(), ladder.end(), etc2_scale) == ladder.end()) { std::printf("❌ --etc2-scale takes 1 or a factor of --texture-ladder (got %d)\n", etc2_scale); return 1; }
   std::vector<uint8_t> raw; if (!read_file(argv[1], raw)) { std::printf("❌ cannot read %s\n", argv[1]); return 1; }
@@ -151,6 +160,23 @@ int main(int argc, char **argv) {
   if (!cfg.images_path.empty() && (!make_dirs(tex_dir) || (want_etc2 && !make_dirs(etc_dir)))) { std::printf("❌ cannot create %s\n", tex_dir.c_str()); return 1; }
   if (want_etc2 && cfg.images_path.empty()) { std::printf("❌ --targets etc2 needs ImagesPath (the raw target is transcoded while the segments are encoded)\n"); return 1; }
   if (!ladder.empty() && cfg.images_path.empty()) { std::printf("❌ --texture-ladder needs ImagesPath (the rungs are downscaled from the images while the segments are encoded)\n"); return 1; }
+  // --mipmaps: the levels a size gets, and the divisibility rule of the chain (include/uvol_codec.h) judged on the first image's IHDR for the full
+  // size and every rung, before any file is written
+  auto mip_levels_for = [&](uint32_t mw, uint32_t mh) { const int full = uvol_mip_level_count(mw, mh); return mipmaps <= 0 || mipmaps > full ? full : mipmaps; };
+  if (mipmaps >= 0 && !cfg.images_path.empty()) {
+    char p0[4096]; std::snprintf(p0, sizeof p0, convert_pounds_to_c_style(cfg.images_path).c_str(), cfg.ktx2_first_file);
+    std::vector<uint8_t> png; uint32_t iw = 0, ih = 0;
+    if (read_file(p0, png) && png.size() >= 24 && !std::memcmp(&png[12], "IHDR", 4)) { iw = (uint32_t)png[16] << 24 | (uint32_t)png[17] << 16 | (uint32_t)png[18] << 8 | png[19]; ih = (uint32_t)png[20] << 24 | (uint32_t)png[21] << 16 | (uint32_t)png[22] << 8 | png[23]; }
+    std::vector<int> fs(1, 1); fs.insert(fs.end(), ladder.begin(), ladder.end());
+    for (int f : fs) {
+      const uint32_t mw = (iw + (uint32_t)f - 1) / (uint32_t)f, mh = (ih + (uint32_t)f - 1) / (uint32_t)f;
+      if (!mw || !mh) continue;                            // (an unreadable first image fails in the texture stage, with its own message)
+      for (int v = 1; v < mip_levels_for(mw, mh); v++) {
+        const uint32_t lw = std::max(1u, mw >> v), lh = std::max(1u, mh >> v);
+        if (mw % lw || mh % lh) { std::printf("❌ --mipmaps: level %d of %u x %u is %u x %u, and width / level width, height / level height must be integers (give --mipmaps %d)\n", v, mw, mh, lw, lh, v); return 1; }
+      }
+    }
+  }
   auto rung_dir = [&](uint32_t rw, uint32_t rh) { return join(cfg.output_directory, "texture_ktx2_" + std::to_string(rw) + "x" + std::to_string(rh) + "_baseColor_default"); };
   int pad = 5;
   std::atomic<int> geo_failed{-1};
@@ -422,6 +448,18 @@ int main(int argc, char **argv) {
         // fewer layers one call each
         auto encode_set = [&](const std::vector<std::vector<const uint8_t *>> &lp, bool dev, uint32_t ew, uint32_t eh, std::vector<std::unique_ptr<uint8_t[]>> &outs, std::vector<size_t> &lens) {
           std::vector<size_t> full; for (size_t s = 0; s < T->ns; s++) if ((int)lp[s].size() == B) full.push_back(s);
+          if (mipmaps >= 0) {                              // --mipmaps: the same sets through the entry point that writes the levels
+            const int nlev = mip_levels_for(ew, eh);
+            auto run = [&](const std::vector<size_t> &segs, int nl) {
+              std::vector<const uint8_t *> ptrs; std::vector<uint8_t *> op; std::vector<size_t> caps, ln(segs.size(), 0); std::vector<int> st(segs.size(), UVOL_OK);
+              for (size_t s : segs) { for (size_t k = 0; k < lp[s].size(); k++) ptrs.push_back(lp[s][k]); const size_t cap = uvol_texture_bound_mips(ew, eh, nl, nlev); outs[s].reset(new uint8_t[cap]); op.push_back(outs[s].get()); caps.push_back(cap); }
+              if (uvol_encode_texture_segments_mips(tctxs[g], ptrs.data(), (int)segs.size(), nl, ew, eh, dev ? 1 : 0, nlev, op.data(), caps.data(), ln.data(), st.data()) != UVOL_OK) { fail(starts[s0 + segs[0]], uvol_last_error(tctxs[g])); return; }
+              for (size_t q = 0; q < segs.size(); q++) { lens[segs[q]] = ln[q]; if (st[q] != UVOL_OK && tex_failed < 0) fail(starts[s0 + segs[q]], uvol_last_error(tctxs[g])); }
+            };
+            if (!full.empty()) run(full, B);
+            for (size_t s = 0; s < T->ns && tex_failed < 0; s++) if ((int)lp[s].size() != B) run(std::vector<size_t>(1, s), (int)lp[s].size());
+            return;
+          }
           if (!full.empty()) {
             std::vector<const uint8_t *> ptrs; std::vector<uint8_t *> op; std::vector<size_t> caps, ln(full.size(), 0);
             for (size_t s : full) { for (size_t k = 0; k < lp[s].size(); k++) ptrs.push_back(lp[s][k]); const size_t cap = uvol_texture_bound(ew, eh, B); outs[s].reset(new uint8_t[cap]); op.push_back(outs[s].get()); caps.push_back(cap); }

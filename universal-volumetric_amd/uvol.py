@@ -70,7 +70,9 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_host_alloc", "uvol_host_free", "uvol_inflate_png_batch_dev", "uvol_png_status",
            "uvol_mesh_bound_mat", "uvol_encode_mesh_batch_mat", "uvol_encode_mesh_batch_mat_async", "uvol_decode_mesh_batch_mat", "uvol_parse_obj_batch_dev_mat",
            "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed", "uvol_downscale_rgba_batch_dev",
-           "uvol_etc2_rgb_bound", "uvol_encode_etc2_rgb_batch"]
+           "uvol_etc2_rgb_bound", "uvol_encode_etc2_rgb_batch",
+           "uvol_mip_level_count", "uvol_mipchain_rgba_batch_dev", "uvol_texture_bound_mips", "uvol_encode_texture_segments_mips", "uvol_ktx2_levels",
+           "uvol_transcode_texture_segments_level"]
 
 
 def load(path=None):
@@ -130,6 +132,14 @@ def load(path=None):
     if hasattr(L, "uvol_encode_etc2_rgb_batch"):      # (a build that predates the entry point still loads: tools/etc2_direct_timing.py may time one beside this build)
         L.uvol_etc2_rgb_bound.argtypes = [C.c_uint32, C.c_uint32]; L.uvol_etc2_rgb_bound.restype = C.c_size_t
         L.uvol_encode_etc2_rgb_batch.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_int]
+    if hasattr(L, "uvol_mipchain_rgba_batch_dev"):      # (a build that predates the mip levels still loads: tools/mipchain_timing.py may time one beside this build)
+        L.uvol_mip_level_count.argtypes = [C.c_uint32, C.c_uint32]
+        L.uvol_mipchain_rgba_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]
+        L.uvol_texture_bound_mips.argtypes = [C.c_uint32, C.c_uint32, C.c_int, C.c_int]; L.uvol_texture_bound_mips.restype = C.c_size_t
+        L.uvol_encode_texture_segments_mips.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.c_int, C.c_int, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.POINTER(C.c_void_p),
+                                                        C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
+        L.uvol_ktx2_levels.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
+        L.uvol_transcode_texture_segments_level.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]
     L.uvol_parse_obj_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_int)]
     L.uvol_encode_mesh_batch_dev_out.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.uvol_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -359,6 +369,37 @@ class Codec:
             raise UvolError(f"downscale_rgba_batch_dev rc={rc}: {self.error()}")
         return [int(p) for p in out]
 
+    def mip_level_count(self, width, height):
+        """uvol_mip_level_count: floor(log2(max(width, height))) + 1, level 0 included."""
+        return int(self.L.uvol_mip_level_count(width, height))
+
+    def mipchain_rgba_batch_dev(self, layers_or_ptrs, width, height, levels=0, slot=0, on_device=None):
+        """uvol_mipchain_rgba_batch_dev: layers of one size -> their mip levels 1 .. levels - 1 (levels=0: the full chain), made on the device in
+        one pass over level 0.  Returns one list per layer of DEVICE pointers, entry v - 1 = level v (max(1, width >> v) x max(1, height >> v)
+        RGBA8) in the context's chain slot, valid until that slot is written again.  layers_or_ptrs / on_device as downscale_rgba_batch_dev."""
+        items = list(layers_or_ptrs); n = len(items)
+        if on_device is None:
+            on_device = n > 0 and all(isinstance(x, int) for x in items)
+        keep = []
+        if on_device:
+            ptrs = (C.c_void_p * n)(*[int(p) if p else None for p in items])
+        else:
+            for a in items:
+                if a is None:
+                    keep.append(None); continue
+                a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+                if a.size != width * height * 4:
+                    raise ValueError("every layer must hold width * height * 4 bytes")
+                keep.append(a)
+            ptrs = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep])
+        full = max(self.mip_level_count(width, height), 1)
+        nl = levels if 1 <= levels <= full else full          # (the array is sized for the longest chain; the library judges `levels`)
+        out = (C.c_void_p * max(n * (full - 1), 1))()
+        rc = self.L.uvol_mipchain_rgba_batch_dev(self.h, ptrs, n, width, height, 1 if on_device else 0, levels, slot, out)
+        if rc != UVOL_OK:
+            raise UvolError(f"mipchain_rgba_batch_dev rc={rc}: {self.error()}")
+        return [[int(out[i * (nl - 1) + v]) for v in range(nl - 1)] for i in range(n)]
+
     def encode_etc2_rgb_batch(self, layers_or_ptrs, width, height, on_device=None, out_dev_ptrs=None, layer_cap=None):
         """uvol_encode_etc2_rgb_batch: RGBA8 layers of one size -> full ETC1 blocks (valid ETC2 RGB8) searched from the source texels, one launch
         for the batch.  layers_or_ptrs: device pointers (ints), or host images (HxWx4 uint8 arrays / bytes of width * height * 4), which are
@@ -583,11 +624,42 @@ class Codec:
             raise UvolError(f"encode_texture_segments_st rc={rc}: {self.error()}")
         return [bufs[i][:lens[i]].tobytes() if st[i] == UVOL_OK else None for i in range(nseg)], list(st)
 
+    def encode_texture_segments_mips(self, segments, levels=0, caps=None, dev_ptrs=None, shape=None):
+        """uvol_encode_texture_segments_mips: every segment -> ONE .ktx2 with `levels` mip levels (0: the full chain; a UASTC context) ->
+        (list of .ktx2 bytes or None, list of status codes).  segments: lists of HxWx4 uint8 arrays; or dev_ptrs = a flat list of
+        n_segments * n_layers device pointers with shape = (width, height, n_layers).  caps: optional output capacities per segment."""
+        if dev_ptrs is not None:
+            w, h, nl = shape; flat = [int(p) for p in dev_ptrs]; nseg = len(flat) // nl
+            ptrs = (C.c_void_p * len(flat))(*flat)
+        else:
+            arrs = [[np.ascontiguousarray(a, dtype=np.uint8) for a in seg] for seg in segments]
+            h, w = arrs[0][0].shape[:2]; nl = len(arrs[0]); nseg = len(arrs)
+            flat = [a for seg in arrs for a in seg]
+            ptrs = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
+        cap = self.L.uvol_texture_bound_mips(w, h, nl, levels) or self.L.uvol_texture_bound(w, h, nl)
+        cl = [cap] * nseg if caps is None else [int(c) for c in caps]
+        bufs = [np.empty(max(c, 1), dtype=np.uint8) for c in cl]
+        outs = (C.c_void_p * nseg)(*[b.ctypes.data for b in bufs]); capa = (C.c_size_t * nseg)(*cl); lens = (C.c_size_t * nseg)(); st = (C.c_int * nseg)()
+        rc = self.L.uvol_encode_texture_segments_mips(self.h, ptrs, nseg, nl, w, h, 0 if dev_ptrs is None else 1, levels, outs, capa, lens, st)
+        if rc != UVOL_OK:
+            raise UvolError(f"encode_texture_segments_mips rc={rc}: {self.error()}")
+        return [bufs[i][:lens[i]].tobytes() if st[i] == UVOL_OK else None for i in range(nseg)], list(st)
+
+    def ktx2_levels(self, data: bytes):
+        """uvol_ktx2_levels: the mip level count of a .ktx2 this codec reads (1 for an ETC1S file)."""
+        n = C.c_uint32()
+        rc = self.L.uvol_ktx2_levels(data, len(data), C.byref(n))
+        if rc != UVOL_OK:
+            raise UvolError(f"uvol_ktx2_levels rc={rc}")
+        return n.value
+
     TARGETS = {"rgba32": (0, 4, False), "etc1": (1, 8, True), "bc7": (2, 16, True), "astc": (3, 16, True), "etc2_rgba": (4, 16, True), "bc1": (5, 8, True), "bc3": (6, 16, True)}
 
-    def transcode_texture_segments_status(self, files, target="rgba32", shape=None):
+    def transcode_texture_segments_status(self, files, target="rgba32", shape=None, level=None):
         """Per-segment results and mixed batches (uvol_transcode_texture_segments_st): files may mix ETC1S and UASTC sources and contain
-        unreadable or corrupt ones -> (list of arrays or None, list of status codes).  shape = (w, h, layers) if the first file is not readable."""
+        unreadable or corrupt ones -> (list of arrays or None, list of status codes).  shape = (w, h, layers) if the first file is not readable.
+        level: the mip level asked of every file (uvol_transcode_texture_segments_level): the arrays have the LEVEL's size; shape stays the
+        files' level-0 shape."""
         files = [bytes(f) for f in files]; n = len(files)
         code, unit, blocks = self.TARGETS[target]
         if shape is None:
@@ -596,11 +668,17 @@ class Codec:
                     shape = self.ktx2_info(f); break
                 except UvolError:
                     continue
-        w, h, nl = shape; bx, by = (w + 3) // 4, (h + 3) // 4
+        w, h, nl = shape
+        if level is not None:
+            w, h = max(1, w >> level), max(1, h >> level)
+        bx, by = (w + 3) // 4, (h + 3) // 4
         outs = [np.zeros((nl, by, bx, unit) if blocks else (nl, h, w, 4), dtype=np.uint8) for _ in range(n)]
         fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
         ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
-        rc = self.L.uvol_transcode_texture_segments_st(self.h, fp, ln, n, ptrs, bx * by * unit if blocks else w * h * 4, 0, code, st)
+        if level is None:
+            rc = self.L.uvol_transcode_texture_segments_st(self.h, fp, ln, n, ptrs, bx * by * unit if blocks else w * h * 4, 0, code, st)
+        else:
+            rc = self.L.uvol_transcode_texture_segments_level(self.h, fp, ln, n, level, ptrs, bx * by * unit if blocks else w * h * 4, code, 0, st)
         if rc != UVOL_OK:
             raise UvolError(f"transcode_texture_segments_st rc={rc}: {self.error()}")
         return [outs[i] if st[i] == UVOL_OK else None for i in range(n)], list(st)
