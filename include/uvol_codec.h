@@ -171,6 +171,65 @@ int uvol_inflate_png_batch_dev(uvol_ctx *ctx, const uint8_t *const *zlib_streams
  * status[i] = UVOL_OK or UVOL_E_INVALID, n <= the images of that call.  status == NULL: the first failure is the return value. */
 int uvol_png_status(uvol_ctx *ctx, int slot, int *status, int n);
 
+/* ---- JPEG textures (additive: uvol_abi_version stays 1) ----
+ * The reference's README names a JPEG as its example texture input (`ImagesPath: Eg: /home/3D/export_[#####].jpg`), and the `basisu` that
+ * scripts/Encoder.py:290 spawns reads .jpg as it reads .png.  The split is the PNG one: the serial bit stream (marker parse, Huffman decode)
+ * stays with the caller (host/uvol_host.cpp read_jpeg_raw; one stream per file, the files of a batch in parallel on host threads), the
+ * data-parallel part - dequantisation, 8 x 8 inverse DCT, chroma upsampling, YCbCr -> RGB - runs on the device into the RGBA8 layers of an
+ * ingest slot.
+ *
+ * THE DECODING RULE.  JPEG fixes neither an IDCT nor an upsampling filter bit for bit, so - as with the downscale filter and the direct etc2
+ * encode - the rule is this project's own and exact in integers: the device kernel, the host reader (read_jpeg) and the NumPy restatement of
+ * tests/jpeg_cases.py agree bit for bit; closeness to libjpeg is measured, not an identity.
+ *
+ * Accepted: baseline sequential DCT (SOF0), 8-bit samples, Huffman coding, ONE scan that holds all components, restart intervals (DRI /
+ * RST0-7) included; one component (grey; its sampling factors are ignored, as the standard says for a single-component scan) or three
+ * components Y, Cb, Cr with chroma at 1 x 1 and luma at 1 x 1 (4:4:4), 2 x 1 (4:2:2) or 2 x 2 (4:2:0); width <= 8192, height <= 16384.
+ * Refused by name (UVOL_E_UNSUPPORTED from the host reader, never a silent wrong decode): progressive (SOF2), extended or 12-bit (SOF1 with
+ * P != 8), lossless or arithmetic-coded (SOF3, SOF9 upwards), four components or any other sampling layout (luma 1 x 2 included), an Adobe
+ * APP14 segment with transform 0 (RGB stored as such), 16-bit quantisation tables, several scans.
+ *
+ * Coefficient layout (what uvol_idct_jpeg_batch_dev takes; also what jpeg_read_coefficients of libjpeg hands a caller): per image, then per
+ * component, the component's blocks in raster order over its block grid padded to whole MCUs - with mcu_w = ceil(W / (8 hmax)),
+ * mcu_h = ceil(H / (8 vmax)) the grid is mcu_w h_c blocks wide and mcu_h v_c blocks high -, each block 64 int16 in natural order
+ * (8 v + u), QUANTISED (not dequantised).  Each image also carries its quantisation tables, one per component: 64 uint16, natural order.
+ *
+ * Per block (every >> is an arithmetic shift; every sum fits 32 bits because of the two clamps):
+ *   dequantise  F[v][u] = clamp(coef[v][u] q[v][u], -32768, 32767)
+ *   cosines     K[x][u] = floor(8192 s_u cos((2 x + 1) u pi / 16) + 0.5) in double, s_0 = 1 / (2 sqrt 2), s_u = 1 / 2 otherwise
+ *               (K[x][0] = 2896; the largest entry is 4017)
+ *   columns     b[y][u] = clamp((sum_v K[y][v] F[v][u] + 1024) >> 11, -32768, 32767)
+ *   rows        p[y][x] = (sum_u K[x][u] b[y][u] + 16384) >> 15
+ *   sample      clamp(p + 128, 0, 255)
+ * Both clamps are inactive on any stream an encoder produced; they keep a hostile stream from overflowing.
+ *
+ * Chroma upsampling.  A component's real extent is cw = ceil(W h_c / hmax) by ch = ceil(H v_c / vmax); the filter runs over that extent, not
+ * over the MCU padding: a neighbour outside it is the sample itself.
+ *   2 x 1   with sample c and its left / right neighbours l / r: out[2 i] = (3 c + l + 1) >> 2, out[2 i + 1] = (3 c + r + 2) >> 2
+ *   2 x 2   vertical step, not rounded: a_even = 3 c + above, a_odd = 3 c + below; horizontal step on those rows:
+ *           out[2 i] = (3 a + a_left + 8) >> 4, out[2 i + 1] = (3 a + a_right + 7) >> 4
+ * Crop to W x H after upsampling.
+ *
+ * Colour, with cb = Cb - 128, cr = Cr - 128: R = Y + ((91881 cr + 32768) >> 16), G = Y - ((22554 cb + 46802 cr + 32768) >> 16),
+ * B = Y + ((116130 cb + 32768) >> 16), each clamped to 0 .. 255; grey gives R = G = B = Y.  Alpha is 255, top row first. */
+typedef struct {
+  uint32_t width, height;
+  int components;        /* 1 or 3 */
+  int luma_h, luma_v;    /* 1 x 1, 2 x 1 or 2 x 2; 1 x 1 for grey */
+} uvol_jpeg_layout;
+/* int16 values per image in the layout above; 0 for a layout outside the rule */
+size_t uvol_jpeg_coeff_count(const uvol_jpeg_layout *layout);
+/* n images of ONE layout, each as its quantised coefficients (coeffs[i]: uvol_jpeg_coeff_count values) and its own quantisation tables
+ * (qtables[i]: components x 64 uint16 - a sequence may change quality from frame to frame), in host memory -> rgba_dev_out[i] = DEVICE
+ * pointer to width * height * 4 bytes in slot `slot` (0 / 1) of the SAME ingest slots uvol_unfilter_png_batch_dev writes, with its ordering
+ * and lifetime: the call returns once the kernels are queued on the ingest stream and the host buffers have been read (pageable memory
+ * is staged, uvol_host_alloc memory is copied from where it lies and the call waits for those copies); the texture, downscale and mip-chain
+ * entry points order themselves behind it; uvol_sync before the caller reads the layers itself; uvol_trim gives the memory back.
+ * n <= 0: UVOL_OK, nothing happens.  UVOL_E_INVALID with a message, before anything runs: a bad slot, a NULL pointer, a layout outside the
+ * rule, a size beyond 8192 x 16384.  Profile groups: jpeg.upload, jpeg.idct. */
+int uvol_idct_jpeg_batch_dev(uvol_ctx *ctx, const int16_t *const *coeffs, const uint16_t *const *qtables, int n,
+                             const uvol_jpeg_layout *layout, int slot, const uint8_t **rgba_dev_out);
+
 /* ---- reduced-resolution texture layers (additive: uvol_abi_version stays 1) ----
  * The player manifest gives every texture target its own `resolution` (reference src/Interfaces.ts:41-73, :113-131), so that one capture is
  * served in several sizes; the raw `etc2` target in particular exists for the devices that cannot afford the transcoder

@@ -404,6 +404,31 @@ int png_wait(uvol_ctx *ctx) {
   }
   return rc;
 }
+// The ingest slots for a second producer (jpeg_ingest.hip): slot `slot` grown to `bytes`, the ingest stream created; the caller queues its
+// work on *stream and then calls png_slot_end, which records the slot's event - png_order_before / png_wait treat the layers as they treat
+// un-filtered ones.  (uvol_ensure runs on the ingest stream, as in png_ingest_batch.)
+int png_slot_begin(uvol_ctx *ctx, int slot, size_t bytes, hipStream_t *stream, uint8_t **base) {
+  PngState *S = ctx->png;
+  if (!S->stream) { if (uvol_make_stream(ctx, &S->stream) != hipSuccess || hipEventCreateWithFlags(&S->done[0], hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&S->done[1], hipEventDisableTiming) != hipSuccess) { ctx->set_error("ingest stream: creation failed"); return UVOL_E_HIP; } }
+  hipStream_t saved = ctx->stream; ctx->stream = S->stream;
+  const int rc = uvol_ensure(ctx, S->rgba[slot], bytes);
+  ctx->stream = saved;
+  if (rc) return rc;
+  S->nstat[slot] = 0;                                      // (uvol_png_status speaks of PNG calls only)
+  *stream = S->stream; *base = (uint8_t *)S->rgba[slot].p;
+  return UVOL_OK;
+}
+int png_slot_end(uvol_ctx *ctx, int slot) {
+  PngState *S = ctx->png;
+  UVOL_HIP_CHECK(ctx, hipEventRecord(S->done[slot], S->stream));
+  S->pending[slot] = true;
+  return UVOL_OK;
+}
+// uvol_trim (after uvol_sync: nothing of the context is in flight): the slots and the upload buffers go back to the device
+void png_trim(uvol_ctx *ctx) {
+  PngState *S = ctx->png; if (!S) return;
+  for (uvol_devbuf *b : { &S->raw, &S->rgba[0], &S->rgba[1], &S->zin }) if (b->p) { (void)hipFree(b->p); b->p = nullptr; b->cap = 0; }
+}
 void png_destroy(uvol_ctx *ctx) {
   PngState *S = ctx->png; if (!S) return;
   if (S->stream) { (void)hipStreamSynchronize(S->stream); (void)hipStreamDestroy(S->stream); }

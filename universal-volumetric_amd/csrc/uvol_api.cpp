@@ -269,7 +269,7 @@ void uvol_ctx_destroy(uvol_ctx *ctx) {
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
   ctx->resolve_profile();
   geo_destroy(ctx); tex_destroy(ctx); uvol_uplink_destroy(ctx);      // (the lanes' streams are synchronised and gone before the slots they read are freed)
-  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); png_destroy(ctx); down_destroy(ctx); mip_destroy(ctx); etc2_destroy(ctx);
+  texdec_destroy(ctx); geodec_destroy(ctx); uastc_destroy(ctx); obj_destroy(ctx); jpeg_destroy(ctx); png_destroy(ctx); down_destroy(ctx); mip_destroy(ctx); etc2_destroy(ctx);
   for (int k = 0; k < 2; k++) { if (ctx->up_pin[k]) (void)hipHostFree(ctx->up_pin[k]); if (ctx->up_ev[k]) (void)hipEventDestroy(ctx->up_ev[k]); }
   for (int k = 0; k < 2; k++) if (ctx->pin_ev[k]) (void)hipEventDestroy(ctx->pin_ev[k]);
   for (int k = 0; k < 2; k++) { if (ctx->dn_pin[k]) (void)hipHostFree(ctx->dn_pin[k]); if (ctx->dn_ev[k]) (void)hipEventDestroy(ctx->dn_ev[k]); }
@@ -304,6 +304,8 @@ int uvol_trim(uvol_ctx *ctx) {
   down_trim(ctx);
   mip_trim(ctx);
   etc2_trim(ctx);
+  jpeg_trim(ctx);
+  png_trim(ctx);
   return rc != UVOL_OK ? rc : (rf != UVOL_OK ? rf : (rx != UVOL_OK ? rx : rt));
 }
 
@@ -737,6 +739,15 @@ int uvol_inflate_png_batch_dev(uvol_ctx *ctx, const uint8_t *const *zlib_streams
   if (!ctx || !zlib_streams || !lens || n < 0 || !rgba_dev_out) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
   return png_ingest_batch(ctx, zlib_streams, lens, n, width, height, channels, slot, rgba_dev_out);
+}
+size_t uvol_jpeg_coeff_count(const uvol_jpeg_layout *layout) { return jpeg_coeff_count(layout); }
+int uvol_idct_jpeg_batch_dev(uvol_ctx *ctx, const int16_t *const *coeffs, const uint16_t *const *qtables, int n, const uvol_jpeg_layout *layout, int slot, const uint8_t **rgba_dev_out) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx) return UVOL_E_INVALID;
+  if (n <= 0) return UVOL_OK;
+  if (!coeffs || !qtables || !layout || !rgba_dev_out) { ctx->set_error("uvol_idct_jpeg_batch_dev: %s is NULL", !coeffs ? "coeffs" : (!qtables ? "qtables" : (!layout ? "layout" : "rgba_dev_out"))); return UVOL_E_INVALID; }
+  (void)hipSetDevice(ctx->device);
+  return jpeg_idct_batch(ctx, coeffs, qtables, n, layout, slot, rgba_dev_out);
 }
 int uvol_downscale_rgba_batch_dev(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t width, uint32_t height, int inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out) {
   UVOL_AFTER_ASYNC(ctx);

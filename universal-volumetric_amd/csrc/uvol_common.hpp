@@ -160,6 +160,7 @@ struct PngState;     // PNG scanlines un-filtered on the device (png_ingest.hip)
 struct DownState;    // RGBA layers downscaled on the device (tex_downscale.hip)
 struct Etc2State;    // RGBA layers encoded to full ETC1 blocks (tex_etc2.hip)
 struct MipState;     // mip chains of RGBA layers made on the device (tex_mipchain.hip)
+struct JpegState;    // JPEG coefficients to RGBA layers on the device (jpeg_ingest.hip)
 
 struct uvol_ctx {
   int device = 0;
@@ -180,6 +181,7 @@ struct uvol_ctx {
   DownState *down = nullptr;      // created by the first uvol_downscale_rgba_batch_dev
   Etc2State *etc2 = nullptr;      // created by the first uvol_encode_etc2_rgb_batch
   MipState *mip = nullptr;        // created by the first uvol_mipchain_rgba_batch_dev / uvol_encode_texture_segments_mips
+  JpegState *jpeg = nullptr;      // created by the first uvol_idct_jpeg_batch_dev
   // enqueue form of the ABI (uvol_*_async + uvol_sync): calls run in order on this context's worker thread
   struct AsyncQ {
     std::mutex m; std::condition_variable cv_work, cv_idle; std::deque<std::function<int()>> q; std::thread th; bool busy = false, stop = false; int first_err = 0; char err[512] = {0};
@@ -271,6 +273,15 @@ int png_wait(uvol_ctx *ctx);
 int png_unfilter_batch(uvol_ctx *ctx, const uint8_t *const *raw, int n, uint32_t w, uint32_t h, int channels, int slot, const uint8_t **rgba_dev_out);
 int png_ingest_batch(uvol_ctx *ctx, const uint8_t *const *raw, const size_t *zlens, int n, uint32_t w, uint32_t h, int channels, int slot, const uint8_t **rgba_dev_out);
 int png_status(uvol_ctx *ctx, int slot, int *status, int n);
+// the ingest slots for a second producer (jpeg_ingest.hip): the slot grown and the ingest stream handed out / the slot's event recorded
+int png_slot_begin(uvol_ctx *ctx, int slot, size_t bytes, hipStream_t *stream, uint8_t **base);
+int png_slot_end(uvol_ctx *ctx, int slot);
+void png_trim(uvol_ctx *ctx);
+// uvol_idct_jpeg_batch_dev (jpeg_ingest.hip); the state is created by the first call
+size_t jpeg_coeff_count(const uvol_jpeg_layout *layout);
+int jpeg_idct_batch(uvol_ctx *ctx, const int16_t *const *coeffs, const uint16_t *const *qtables, int n, const uvol_jpeg_layout *layout, int slot, const uint8_t **rgba_dev_out);
+void jpeg_trim(uvol_ctx *ctx);
+void jpeg_destroy(uvol_ctx *ctx);
 // uvol_downscale_rgba_batch_dev (tex_downscale.hip); the state is created by the first call
 int down_rgba_batch(uvol_ctx *ctx, const uint8_t *const *rgba, int n, uint32_t w, uint32_t h, bool inputs_on_device, int factor, int slot, const uint8_t **rgba_dev_out);
 void down_trim(uvol_ctx *ctx);

@@ -27,7 +27,7 @@ int main(int argc, char **argv) {
   if (files.empty()) { std::fprintf(stderr, "No input files\n"); return 1; }
   std::vector<uvolh::Image> imgs(files.size()); std::vector<const uint8_t *> ptrs; std::string err;
   for (size_t k = 0; k < files.size(); k++) {
-    if (!uvolh::read_png(files[k], imgs[k], err)) { std::fprintf(stderr, "Failed reading source image: %s\n", err.c_str()); return 1; }
+    if (!uvolh::read_image(files[k], imgs[k], err)) {      /* PNG or JPEG, by signature (basisu reads both) */ std::fprintf(stderr, "Failed reading source image: %s\n", err.c_str()); return 1; }
     if (imgs[k].w != imgs[0].w || imgs[k].h != imgs[0].h) { std::fprintf(stderr, "All source images must have the same dimensions\n"); return 1; }
     ptrs.push_back(imgs[k].rgba.data());
   }

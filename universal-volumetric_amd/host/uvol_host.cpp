@@ -455,6 +455,268 @@ int read_png_raw(const std::string &path, PngRaw &out, std::string &err, IngestS
   return 1;
 }
 
+// ------------------------------------------------------------------ JPEG (baseline sequential, 8-bit, Huffman, one scan): include/uvol_codec.h states the rule
+namespace {
+const uint8_t kZigzag[64] = { 0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
+                              35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63 };
+// one Huffman table: codes up to 9 bits from a look-up table (entry = length << 8 | symbol, 0 = longer or none), longer ones by the canonical walk
+struct JHuff {
+  bool defined = false; uint8_t vals[256]; int nvals = 0; uint16_t fast[512]; int maxcode[18]; int mincode[17]; int valptr[17];
+  bool build(const uint8_t *counts, const uint8_t *syms, int n) {
+    nvals = n; std::memcpy(vals, syms, (size_t)n); std::memset(fast, 0, sizeof fast);
+    int code = 0, k = 0;
+    for (int L = 1; L <= 16; L++) {
+      valptr[L] = k; mincode[L] = code;
+      if (code + counts[L - 1] > (1 << L)) return false;        // more codes of this length than the prefix space holds
+      for (int i = 0; i < counts[L - 1]; i++, k++, code++) if (L <= 9) { const int lo = code << (9 - L); for (int f = 0; f < (1 << (9 - L)); f++) fast[lo + f] = (uint16_t)((L << 8) | vals[k]); }
+      maxcode[L] = counts[L - 1] ? code - 1 : -1;
+      code <<= 1;
+    }
+    defined = true; return true;
+  }
+};
+// the scan's bits: byte stuffing (FF 00) removed, nothing read behind a marker or the end of the data
+struct JBits {
+  const uint8_t *d; size_t n, pos; uint64_t buf = 0; int cnt = 0; bool bad = false;
+  void fill() {
+    while (cnt <= 56 && pos < n) {
+      const uint8_t b = d[pos];
+      if (b == 0xff) { if (pos + 1 >= n || d[pos + 1] != 0) break; pos += 2; }      // a marker (or the end): the scan's bits stop here
+      else pos++;
+      buf = (buf << 8) | b; cnt += 8;
+    }
+  }
+  // the next k <= 16 bits; behind the last bit of the scan the look-ahead sees ones (take() then refuses what is not there)
+  uint32_t peek(int k) { if (cnt < k) fill(); return cnt >= k ? (uint32_t)(buf >> (cnt - k)) & ((1u << k) - 1u) : (uint32_t)(((buf << (k - cnt)) | ((1ull << (k - cnt)) - 1ull)) & ((1ull << k) - 1ull)); }
+  void take(int k) { if (k > cnt) { bad = true; cnt = 0; } else cnt -= k; }
+  int bits(int k) { if (!k) return 0; const uint32_t v = peek(k); take(k); return (int)v; }
+  int decode(const JHuff &h) {
+    const uint32_t c16 = peek(16); const uint16_t e = h.fast[c16 >> 7];
+    if (e) { take(e >> 8); return e & 255; }
+    for (int L = 10; L <= 16; L++) { const int c = (int)(c16 >> (16 - L)); if (h.maxcode[L] >= 0 && c <= h.maxcode[L] && c >= h.mincode[L]) { take(L); return h.vals[h.valptr[L] + c - h.mincode[L]]; } }
+    return -1;
+  }
+};
+inline int jpeg_extend(int v, int s) { return s && v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
+const int *jpeg_cos_table() {      // K[x][u] of the rule, computed in double as it says
+  static int K[64]; static const bool once = [] {
+    const double pi = 3.14159265358979323846;
+    for (int x = 0; x < 8; x++) for (int u = 0; u < 8; u++) K[8 * x + u] = (int)std::floor(8192.0 * (u ? 0.5 : 1.0 / (2.0 * std::sqrt(2.0))) * std::cos((2 * x + 1) * u * pi / 16.0) + 0.5);
+    return true; }();
+  (void)once; return K;
+}
+}  // namespace
+
+int read_jpeg_raw_mem(const uint8_t *d, size_t n, const std::string &name, JpegRaw &out, std::string &err) {
+  auto corrupt = [&](const char *why) { err = name + ": " + why; return -1; };
+  auto refuse = [&](const std::string &what) { err = name + ": unsupported JPEG variant: " + what; return 0; };
+  if (n < 4 || d[0] != 0xff || d[1] != 0xd8) return corrupt("not a JPEG");
+  uint16_t qtab[4][64]; bool qdef[4] = { false, false, false, false }, q16 = false;
+  std::unique_ptr<JHuff[]> huff(new JHuff[8]);            // [0..3] DC, [4..7] AC
+  bool sof = false; int ncomp = 0, cid[4] = { 0, 0, 0, 0 }, ch[4] = { 0, 0, 0, 0 }, cv[4] = { 0, 0, 0, 0 }, ctq[4] = { 0, 0, 0, 0 };
+  uint32_t W = 0, H = 0; int adobe = -1; uint32_t ri = 0; int tdc[3] = { 0, 0, 0 }, tac[3] = { 4, 4, 4 };      // the scan's DC / AC tables per component
+  size_t pos = 2;
+  for (;;) {
+    // the next marker: FF, any number of fill FFs, the code
+    if (pos >= n) return corrupt("truncated: no scan");
+    if (d[pos] != 0xff) return corrupt("a marker was expected");
+    while (pos < n && d[pos] == 0xff) pos++;
+    if (pos >= n) return corrupt("truncated in a marker");
+    const int m = d[pos++];
+    if (m == 0xd8 || m == 0x01 || (m >= 0xd0 && m <= 0xd7)) { if (m >= 0xd0 && m <= 0xd7) return corrupt("restart marker out of place"); continue; }
+    if (m == 0xd9) return corrupt("no scan before the end of the image");
+    if (m == 0) return corrupt("a marker was expected");
+    if (pos + 2 > n) return corrupt("truncated in a segment");
+    const size_t L = ((size_t)d[pos] << 8) | d[pos + 1];
+    if (L < 2 || pos + L > n) return corrupt("truncated in a segment");
+    const uint8_t *p = d + pos + 2; const size_t pl = L - 2;
+    if (m == 0xdb) {
+      for (size_t o = 0; o < pl;) {
+        const int pq = p[o] >> 4, tq = p[o] & 15; o++;
+        if (pq > 1 || tq > 3) return corrupt("bad quantisation table header");
+        const size_t need = pq ? 128 : 64; if (o + need > pl) return corrupt("truncated quantisation table");
+        for (int i = 0; i < 64; i++) qtab[tq][kZigzag[i]] = pq ? (uint16_t)((p[o + 2 * i] << 8) | p[o + 2 * i + 1]) : p[o + i];
+        if (pq) q16 = true;
+        qdef[tq] = true; o += need;
+      }
+    } else if (m == 0xc4) {
+      for (size_t o = 0; o < pl;) {
+        const int tc = p[o] >> 4, th = p[o] & 15; o++;
+        if (tc > 1 || th > 3) return corrupt("bad Huffman table header");
+        if (o + 16 > pl) return corrupt("truncated Huffman table");
+        int tot = 0; for (int i = 0; i < 16; i++) tot += p[o + i];
+        if (tot > 256 || o + 16 + (size_t)tot > pl) return corrupt("truncated Huffman table");
+        if (!huff[4 * tc + th].build(p + o, p + o + 16, tot)) return corrupt("over-subscribed Huffman table");
+        o += 16 + (size_t)tot;
+      }
+    } else if (m == 0xc0 || m == 0xc1) {
+      if (sof) return corrupt("a second frame header");
+      if (pl < 6) return corrupt("truncated frame header");
+      const int P = p[0]; H = ((uint32_t)p[1] << 8) | p[2]; W = ((uint32_t)p[3] << 8) | p[4]; ncomp = p[5];
+      if (P != 8) return refuse(std::to_string(P) + "-bit samples (extended sequential, SOF1)");
+      if (ncomp < 1 || pl < 6 + 3 * (size_t)ncomp) return corrupt("truncated frame header");
+      if (ncomp == 4) return refuse("four components (CMYK / YCCK)");
+      if (ncomp != 1 && ncomp != 3) return refuse(std::to_string(ncomp) + " components");
+      for (int c = 0; c < ncomp; c++) { cid[c] = p[6 + 3 * c]; ch[c] = p[7 + 3 * c] >> 4; cv[c] = p[7 + 3 * c] & 15; ctq[c] = p[8 + 3 * c]; if (ch[c] < 1 || ch[c] > 4 || cv[c] < 1 || cv[c] > 4 || ctq[c] > 3) return corrupt("bad component in the frame header"); }
+      if (!W) return corrupt("width 0");
+      if (!H) return refuse("height 0 (defined later by a DNL marker)");
+      if (W > 8192 || H > 16384) return refuse("image larger than 8192 x 16384");
+      if (ncomp == 1) { ch[0] = cv[0] = 1; }
+      else if (ch[1] != 1 || cv[1] != 1 || ch[2] != 1 || cv[2] != 1 || !((ch[0] == 1 && cv[0] == 1) || (ch[0] == 2 && cv[0] == 1) || (ch[0] == 2 && cv[0] == 2))) {
+        char b[96]; std::snprintf(b, sizeof b, "sampling layout %dx%d %dx%d %dx%d (luma 1x1, 2x1 or 2x2 with chroma 1x1)", ch[0], cv[0], ch[1], cv[1], ch[2], cv[2]); return refuse(b);
+      }
+      sof = true;
+    } else if (m == 0xc2) return refuse("progressive (SOF2)");
+    else if (m == 0xc3 || m == 0xc5 || m == 0xc6 || m == 0xc7 || m == 0xc8) return refuse(m == 0xc3 ? "lossless (SOF3)" : "hierarchical or reserved frame (SOF" + std::to_string(m - 0xc0) + ")");
+    else if (m >= 0xc9 && m <= 0xcf && m != 0xcc) return refuse("arithmetic coding (SOF" + std::to_string(m - 0xc0) + ")");
+    else if (m == 0xcc) return refuse("arithmetic coding (DAC)");
+    else if (m == 0xee) { if (pl >= 12 && !std::memcmp(p, "Adobe", 5)) adobe = p[11]; }
+    else if (m == 0xdd) { if (pl < 2) return corrupt("truncated restart interval"); ri = ((uint32_t)p[0] << 8) | p[1]; }
+    else if (m == 0xda) {
+      if (!sof) return corrupt("SOS before SOF");
+      if (pl < 1) return corrupt("truncated scan header");
+      const int ns = p[0];
+      if (ns < 1 || ns > 4 || pl < 4 + 2 * (size_t)ns) return corrupt("truncated scan header");
+      if (ns != ncomp) return refuse("several scans (a scan that holds " + std::to_string(ns) + " of " + std::to_string(ncomp) + " components)");
+      if (adobe == 0 && ncomp == 3) return refuse("Adobe APP14 transform 0 (RGB stored as such)");
+      if (q16) return refuse("16-bit quantisation tables");
+      int td[4], ta[4];
+      for (int c = 0; c < ns; c++) {
+        if (p[1 + 2 * c] != cid[c]) return corrupt("scan component out of order");
+        td[c] = p[2 + 2 * c] >> 4; ta[c] = p[2 + 2 * c] & 15;
+        if (td[c] > 3 || ta[c] > 3) return corrupt("bad table selector in the scan header");
+        if (!huff[td[c]].defined || !huff[4 + ta[c]].defined) return corrupt("missing Huffman table");
+        if (!qdef[ctq[c]]) return corrupt("missing quantisation table");
+        tdc[c] = td[c]; tac[c] = 4 + ta[c];
+      }
+      if (p[1 + 2 * ns] != 0 || p[2 + 2 * ns] != 63 || p[3 + 2 * ns] != 0) return corrupt("spectral selection of a scan that is not baseline");
+      pos += L;
+      break;
+    }
+    pos += L;
+  }
+  // the layout of include/uvol_codec.h
+  const uint32_t hs = (uint32_t)ch[0], vs = (uint32_t)cv[0], mw = (W + 8 * hs - 1) / (8 * hs), mh = (H + 8 * vs - 1) / (8 * vs);
+  uint32_t bw[3] = { 0, 0, 0 }, boff[3] = { 0, 0, 0 }, nb = 0;
+  for (int c = 0; c < ncomp; c++) { bw[c] = mw * (uint32_t)ch[c]; boff[c] = nb; nb += bw[c] * mh * (uint32_t)cv[c]; }
+  if ((uint64_t)nb * 2 > (uint64_t)(n - pos) * 8) return corrupt("truncated: the scan cannot hold its blocks");      // (a block is two codes at least; also bounds the allocation by the file)
+  out.w = W; out.h = H; out.components = ncomp; out.luma_h = (int)hs; out.luma_v = (int)vs;
+  out.qt.resize((size_t)ncomp * 64);
+  for (int c = 0; c < ncomp; c++) std::memcpy(&out.qt[(size_t)c * 64], qtab[ctq[c]], 128);
+  out.coef.assign((size_t)nb * 64, 0);
+  // the scan
+  JBits B{ d, n, pos };
+  int pred[3] = { 0, 0, 0 };
+  const uint32_t nmcu = mw * mh; uint32_t todo = ri; int rst = 0;
+  for (uint32_t mcu = 0; mcu < nmcu; mcu++) {
+    if (ri && todo == 0) {
+      // a restart interval ends: the bits left are padding, the marker RSTn follows (fill bytes allowed before it)
+      B.cnt = 0; B.buf = 0;
+      size_t q = B.pos;
+      if (q >= n || d[q] != 0xff) return corrupt("restart marker out of place");
+      while (q < n && d[q] == 0xff) q++;
+      if (q >= n || d[q] != 0xd0 + rst) return corrupt("restart marker out of place");
+      B.pos = q + 1; rst = (rst + 1) & 7; todo = ri; pred[0] = pred[1] = pred[2] = 0;
+    }
+    const uint32_t mx = mcu % mw, my = mcu / mw;
+    for (int c = 0; c < ncomp; c++) {
+      const JHuff &hd = huff[tdc[c]], &ha = huff[tac[c]];
+      for (int v = 0; v < cv[c]; v++) for (int h = 0; h < ch[c]; h++) {
+        int16_t *blk = &out.coef[((size_t)boff[c] + (size_t)(my * (uint32_t)cv[c] + (uint32_t)v) * bw[c] + mx * (uint32_t)ch[c] + (uint32_t)h) * 64];
+        const int s = B.decode(hd);
+        if (s < 0) return corrupt(B.bad ? "truncated in the scan" : "a code that no Huffman table has");
+        if (s > 15) return corrupt("DC category out of range");
+        pred[c] += jpeg_extend(B.bits(s), s);
+        if (pred[c] < -32768 || pred[c] > 32767) return corrupt("DC coefficient out of range");
+        blk[0] = (int16_t)pred[c];
+        for (int k = 1; k < 64;) {
+          const int rs = B.decode(ha);
+          if (rs < 0) return corrupt(B.bad ? "truncated in the scan" : "a code that no Huffman table has");
+          const int r = rs >> 4, sz = rs & 15;
+          if (!sz) { if (r != 15) break; k += 16; if (k > 64) return corrupt("a run past coefficient 63"); continue; }
+          k += r; if (k > 63) return corrupt("a run past coefficient 63");
+          blk[kZigzag[k]] = (int16_t)jpeg_extend(B.bits(sz), sz); k++;
+        }
+        if (B.bad) return corrupt("truncated in the scan");
+      }
+    }
+    if (ri) todo--;
+  }
+  // behind the scan: fill, then EOI; another scan is a variant the rule refuses
+  for (size_t q = B.pos; q + 1 < n; q++) if (d[q] == 0xff && d[q + 1] != 0 && d[q + 1] != 0xff) { if (d[q + 1] == 0xda) return refuse("several scans"); if (d[q + 1] == 0xd9) break; if (d[q + 1] >= 0xd0 && d[q + 1] <= 0xd7) return corrupt("restart marker out of place"); }
+  return 1;
+}
+
+void jpeg_decode_rgba(const JpegRaw &J, uint8_t *rgba) {
+  const int *K = jpeg_cos_table();
+  const uint32_t W = J.w, H = J.h, hs = (uint32_t)J.luma_h, vs = (uint32_t)J.luma_v, mw = (W + 8 * hs - 1) / (8 * hs), mh = (H + 8 * vs - 1) / (8 * vs);
+  std::vector<uint8_t> plane[3]; uint32_t pitch[3] = { 0, 0, 0 }, cw[3] = { 0, 0, 0 }, chh[3] = { 0, 0, 0 }; size_t boff = 0;
+  for (int c = 0; c < J.components; c++) {
+    const uint32_t h = c ? 1 : hs, v = c ? 1 : vs, bw = mw * h, bh = mh * v;
+    pitch[c] = bw * 8; cw[c] = (W * h + hs - 1) / hs; chh[c] = (H * v + vs - 1) / vs;
+    plane[c].resize((size_t)pitch[c] * bh * 8);
+    const uint16_t *q = &J.qt[(size_t)c * 64];
+    for (uint32_t by = 0; by < bh; by++) for (uint32_t bx = 0; bx < bw; bx++) {
+      const int16_t *cf = &J.coef[(boff + (size_t)by * bw + bx) * 64];
+      int F[64], b[64];
+      for (int i = 0; i < 64; i++) { const int v2 = (int)cf[i] * (int)q[i]; F[i] = v2 < -32768 ? -32768 : (v2 > 32767 ? 32767 : v2); }
+      for (int y = 0; y < 8; y++) for (int u = 0; u < 8; u++) {
+        int s = 0; for (int vv = 0; vv < 8; vv++) s += K[8 * y + vv] * F[8 * vv + u];
+        s = (s + 1024) >> 11; b[8 * y + u] = s < -32768 ? -32768 : (s > 32767 ? 32767 : s);
+      }
+      for (int y = 0; y < 8; y++) for (int x = 0; x < 8; x++) {
+        int s = 0; for (int u = 0; u < 8; u++) s += K[8 * x + u] * b[8 * y + u];
+        s = ((s + 16384) >> 15) + 128;
+        plane[c][((size_t)by * 8 + (size_t)y) * pitch[c] + (size_t)bx * 8 + (size_t)x] = (uint8_t)(s < 0 ? 0 : (s > 255 ? 255 : s));
+      }
+    }
+    boff += (size_t)bw * bh;
+  }
+  auto nbr = [](uint32_t i, long j, uint32_t n) { return (j < 0 || j >= (long)n) ? i : (uint32_t)j; };
+  for (uint32_t y = 0; y < H; y++) for (uint32_t x = 0; x < W; x++) {
+    uint8_t *o = rgba + ((size_t)y * W + x) * 4; const int Y = plane[0][(size_t)y * pitch[0] + x];
+    o[3] = 255;
+    if (J.components == 1) { o[0] = o[1] = o[2] = (uint8_t)Y; continue; }
+    int cc[2];
+    for (int c = 1; c <= 2; c++) {
+      const uint8_t *P = plane[c].data(); const size_t p = pitch[c];
+      if (hs == 1) cc[c - 1] = P[(size_t)y * p + x];
+      else if (vs == 1) {
+        const uint32_t i = x >> 1; const int s = P[(size_t)y * p + i];
+        cc[c - 1] = (x & 1) ? (3 * s + P[(size_t)y * p + nbr(i, (long)i + 1, cw[c])] + 2) >> 2 : (3 * s + P[(size_t)y * p + nbr(i, (long)i - 1, cw[c])] + 1) >> 2;
+      } else {
+        const uint32_t i = x >> 1, cy = y >> 1, oy = nbr(cy, (y & 1) ? (long)cy + 1 : (long)cy - 1, chh[c]), j = nbr(i, (x & 1) ? (long)i + 1 : (long)i - 1, cw[c]);
+        const int am = 3 * P[(size_t)cy * p + i] + P[(size_t)oy * p + i], an = 3 * P[(size_t)cy * p + j] + P[(size_t)oy * p + j];
+        cc[c - 1] = (3 * am + an + ((x & 1) ? 7 : 8)) >> 4;
+      }
+    }
+    const int cb = cc[0] - 128, cr = cc[1] - 128;
+    const int R = Y + ((91881 * cr + 32768) >> 16), G = Y - ((22554 * cb + 46802 * cr + 32768) >> 16), Bv = Y + ((116130 * cb + 32768) >> 16);
+    o[0] = (uint8_t)(R < 0 ? 0 : (R > 255 ? 255 : R)); o[1] = (uint8_t)(G < 0 ? 0 : (G > 255 ? 255 : G)); o[2] = (uint8_t)(Bv < 0 ? 0 : (Bv > 255 ? 255 : Bv));
+  }
+}
+
+int read_jpeg_raw(const std::string &path, JpegRaw &out, std::string &err, IngestScratch *scratch) {
+  IngestScratch local; IngestScratch &S = scratch ? *scratch : local;
+  if (!read_file(path, S.file)) { err = "cannot read " + path; return -1; }
+  return read_jpeg_raw_mem(S.file.data(), S.file.size(), path, out, err);
+}
+bool read_jpeg(const std::string &path, Image &img, std::string &err, IngestScratch *scratch) {
+  JpegRaw J;
+  if (read_jpeg_raw(path, J, err, scratch) != 1) return false;
+  img.w = J.w; img.h = J.h; img.rgba.resize((size_t)J.w * J.h * 4);
+  jpeg_decode_rgba(J, img.rgba.data());
+  return true;
+}
+bool is_jpeg_file(const std::string &path) {
+  uint8_t s[2] = { 0, 0 }; FILE *f = std::fopen(path.c_str(), "rb"); if (!f) return false;
+  const size_t got = std::fread(s, 1, 2, f); std::fclose(f);
+  return got == 2 && s[0] == 0xff && s[1] == 0xd8;
+}
+bool read_image(const std::string &path, Image &img, std::string &err, IngestScratch *scratch) {
+  return is_jpeg_file(path) ? read_jpeg(path, img, err, scratch) : read_png(path, img, err, scratch);
+}
+
 // ------------------------------------------------------------------ frame accounting (scripts/Encoder.py:103-154)
 static void split_path(const std::string &p, std::string &dir, std::string &base) { size_t k = p.find_last_of('/'); if (k == std::string::npos) { dir = ""; base = p; } else { dir = p.substr(0, k); base = p.substr(k + 1); } }
 bool check_total_frames(const std::string &drc_pat, const std::string &ktx2_pat, int batch, double geo_rate, double tex_rate, FrameCounts &out, std::string &err) {
@@ -627,5 +889,28 @@ int uvolh_read_obj_arrays(const char *path, float *pos, float *uv, float *nrm, u
 int uvolh_read_png(const char *path, unsigned *wh, unsigned char *rgba, size_t cap) {
   uvolh::Image im; std::string err; if (!uvolh::read_png(path, im, err)) return -1;
   wh[0] = im.w; wh[1] = im.h; if (rgba && cap >= im.rgba.size()) std::memcpy(rgba, im.rgba.data(), im.rgba.size()); return 0;
+}
+// test hooks for the JPEG reader, on a file held in memory.  Each returns read_jpeg_raw's status (1 done, 0 a refused variant, -1 corrupt) and
+// leaves the message in err (errcap bytes, NUL-terminated); -2: an output buffer is too small.
+static int jpeg_hook(const unsigned char *data, size_t n, uvolh::JpegRaw &J, char *err, size_t errcap) {
+  std::string e; const int r = uvolh::read_jpeg_raw_mem(data, n, "jpeg", J, e);
+  if (err && errcap) { std::snprintf(err, errcap, "%s", e.c_str()); }
+  return r;
+}
+// out5 = { width, height, components, luma_h, luma_v }
+int uvolh_jpeg_layout(const unsigned char *data, size_t n, unsigned *out5, char *err, size_t errcap) {
+  uvolh::JpegRaw J; const int r = jpeg_hook(data, n, J, err, errcap); if (r != 1) return r;
+  out5[0] = J.w; out5[1] = J.h; out5[2] = (unsigned)J.components; out5[3] = (unsigned)J.luma_h; out5[4] = (unsigned)J.luma_v; return 1;
+}
+// coef: the quantised coefficients in the layout of include/uvol_codec.h (cap_values int16); qt: components x 64 uint16 (cap_qt values)
+int uvolh_jpeg_coeffs(const unsigned char *data, size_t n, short *coef, size_t cap_values, unsigned short *qt, size_t cap_qt, char *err, size_t errcap) {
+  uvolh::JpegRaw J; const int r = jpeg_hook(data, n, J, err, errcap); if (r != 1) return r;
+  if (J.coef.size() > cap_values || J.qt.size() > cap_qt) return -2;
+  std::memcpy(coef, J.coef.data(), J.coef.size() * 2); std::memcpy(qt, J.qt.data(), J.qt.size() * 2); return 1;
+}
+int uvolh_jpeg_decode_rgba(const unsigned char *data, size_t n, unsigned char *rgba, size_t cap, char *err, size_t errcap) {
+  uvolh::JpegRaw J; const int r = jpeg_hook(data, n, J, err, errcap); if (r != 1) return r;
+  if ((size_t)J.w * J.h * 4 > cap) return -2;
+  uvolh::jpeg_decode_rgba(J, rgba); return 1;
 }
 }

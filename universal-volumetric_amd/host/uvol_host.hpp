@@ -64,6 +64,23 @@ bool read_png(const std::string &path, Image &img, std::string &err, IngestScrat
 // bytes).  1: done; 0: a variant the device path does not take (16-bit, palette, grey, wider than 8192: use read_png); -1: error (err set)
 struct PngRaw { uint32_t w = 0, h = 0; int ch = 0; std::vector<uint8_t> raw; };      // raw: the inflated scanlines, or (keep_deflated) the zlib stream itself
 int read_png_raw(const std::string &path, PngRaw &out, std::string &err, IngestScratch *scratch = nullptr, bool keep_deflated = false);
+// JPEG (the reference's README names one as its example ImagesPath; `basisu` reads .jpg as it reads .png).  The decoding rule is stated in
+// include/uvol_codec.h: baseline sequential DCT, 8-bit, Huffman, one scan, grey or Y Cb Cr at 4:4:4 / 4:2:2 / 4:2:0, restart intervals.
+// read_jpeg_raw: marker parse + Huffman decode only - the layout, the quantisation tables (one per component, 64 values in natural order)
+// and the QUANTISED coefficients in the layout uvol_idct_jpeg_batch_dev takes.  1: done; 0: a variant the rule refuses (err names the feature:
+// progressive, 12-bit, lossless, arithmetic, four components, another sampling layout, Adobe transform 0, 16-bit tables, several scans,
+// larger than 8192 x 16384) - there is NO host fallback for those; -1: a corrupt or truncated file (err set).  The bytes are untrusted: every
+// read is bounded by the file, every write by the arrays, every loop by the block count.
+struct JpegRaw { uint32_t w = 0, h = 0; int components = 0, luma_h = 1, luma_v = 1; std::vector<uint16_t> qt; std::vector<int16_t> coef; };
+int read_jpeg_raw(const std::string &path, JpegRaw &out, std::string &err, IngestScratch *scratch = nullptr);
+int read_jpeg_raw_mem(const uint8_t *data, size_t n, const std::string &name, JpegRaw &out, std::string &err);
+// the rest of the decode on the host, by the same rule, bit-identical to the device: rgba = w * h * 4 bytes, alpha 255, top row first
+void jpeg_decode_rgba(const JpegRaw &j, uint8_t *rgba);
+// the whole decode on the host (the fallback and the yardstick, as read_png is for PNG); false: refused or corrupt (err says which)
+bool read_jpeg(const std::string &path, Image &img, std::string &err, IngestScratch *scratch = nullptr);
+// by signature, not by extension: FF D8 is a JPEG, anything else goes to the PNG reader (which words its own error)
+bool is_jpeg_file(const std::string &path);
+bool read_image(const std::string &path, Image &img, std::string &err, IngestScratch *scratch = nullptr);      // read_jpeg or read_png, by signature
 // CPUs this process may actually use: the cgroup v2 quota (cpu.max) when there is one, else the hardware thread count.  A container
 // that sees 256 hardware threads under a 16-CPU quota gets SLOWER with more than ~16 runnable threads (measured: DESIGN section 6).
 unsigned effective_cpus();

@@ -82,7 +82,7 @@ int main(int argc, char **argv) {
     else if (!std::strcmp(argv[i], "--batch-frames") && i + 1 < argc) frames_per_batch = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--ingest-threads") && i + 1 < argc) ingest_threads = std::atoi(argv[++i]);
     else if (!std::strcmp(argv[i], "--force")) force = true;
-    else if (!std::strcmp(argv[i], "--host-png-unfilter")) host_png = true;       // PNG scanlines un-filtered by the ingest threads (as until round 3) instead of on the GPU
+    else if (!std::strcmp(argv[i], "--host-png-unfilter")) host_png = true;       // PNG scanlines un-filtered by the ingest threads (as until round 3) instead of on the GPU; JPEG files are decoded whole on the host too (read_jpeg: IDCT, upsampling and colour by the same rule)
     else if (!std::strcmp(argv[i], "--pinned-text")) pinned_text = true;            // OBJ files read straight into page-locked memory (no staging copy before the upload)
     else if (!std::strcmp(argv[i], "--device-inflate")) dev_inflate = true;        // the PNGs' zlib streams inflated on the GPU too (k_inflate: one wave per image; pays with many images per call, see --tex-batch-frames)
     else if (!std::strcmp(argv[i], "--tex-batch-frames") && i + 1 < argc) tex_batch_frames = std::atoi(argv[++i]);      // images per texture call (default: --batch-frames)
@@ -166,7 +166,8 @@ int main(int argc, char **argv) {
   if (mipmaps >= 0 && !cfg.images_path.empty()) {
     char p0[4096]; std::snprintf(p0, sizeof p0, convert_pounds_to_c_style(cfg.images_path).c_str(), cfg.ktx2_first_file);
     std::vector<uint8_t> png; uint32_t iw = 0, ih = 0;
-    if (read_file(p0, png) && png.size() >= 24 && !std::memcmp(&png[12], "IHDR", 4)) { iw = (uint32_t)png[16] << 24 | (uint32_t)png[17] << 16 | (uint32_t)png[18] << 8 | png[19]; ih = (uint32_t)png[20] << 24 | (uint32_t)png[21] << 16 | (uint32_t)png[22] << 8 | png[23]; }
+    if (is_jpeg_file(p0)) { JpegRaw j0; std::string e0; if (read_jpeg_raw(p0, j0, e0) == 1) { iw = j0.w; ih = j0.h; } }
+    else if (read_file(p0, png) && png.size() >= 24 && !std::memcmp(&png[12], "IHDR", 4)) { iw = (uint32_t)png[16] << 24 | (uint32_t)png[17] << 16 | (uint32_t)png[18] << 8 | png[19]; ih = (uint32_t)png[20] << 24 | (uint32_t)png[21] << 16 | (uint32_t)png[22] << 8 | png[23]; }
     std::vector<int> fs(1, 1); fs.insert(fs.end(), ladder.begin(), ladder.end());
     for (int f : fs) {
       const uint32_t mw = (iw + (uint32_t)f - 1) / (uint32_t)f, mh = (ih + (uint32_t)f - 1) / (uint32_t)f;
@@ -345,6 +346,7 @@ int main(int argc, char **argv) {
     const int segs_per_call = std::max(1, (tex_batch_frames > 0 ? tex_batch_frames : frames_per_batch) / std::max(1, cfg.ktx2_batch_size));
     struct TexBatch { size_t s0 = 0, ns = 0; std::vector<std::vector<Image>> imgs; std::vector<std::vector<Image>> spare; std::string err; int bad = -1;
                       bool dev = false; int slot = 0; std::vector<std::vector<PngRaw>> raws;        // dev: the images are INFLATED scanlines, un-filtered on the GPU
+                      bool jpeg = false; std::vector<std::vector<JpegRaw>> jraws;                     // dev && jpeg: the images are JPEG coefficients (read_jpeg_raw), IDCT on the GPU
                       std::vector<std::vector<const uint8_t *>> dptr; bool issued = false; };   // ... their RGBA layers in HBM once the un-filter call is queued
     for (int g = 0; g < n_gpus; g++) tex_threads.emplace_back([&, g] {
       const size_t lo = starts.size() * (size_t)g / n_gpus, hi = starts.size() * (size_t)(g + 1) / n_gpus;       // = shard_plan's segment block
@@ -367,17 +369,35 @@ int main(int argc, char **argv) {
         if (!host_png) {
           if (T->raws.size() < T->ns) T->raws.resize(T->ns);
           for (size_t s = 0; s < T->ns; s++) if (T->raws[s].size() < (size_t)B) T->raws[s].resize((size_t)B);
-          std::atomic<int> odd{0};
+          if (T->jraws.size() < T->ns) T->jraws.resize(T->ns);
+          for (size_t s = 0; s < T->ns; s++) if (T->jraws[s].size() < (size_t)B) T->jraws[s].resize((size_t)B);
+          std::atomic<int> odd{0}, n_jpeg{0}, n_png{0}; std::atomic<long> jpeg_us{0};
           parallel_for_w(T->ns * (size_t)B, tex_ingest, [&](size_t j, size_t wk) {
             const size_t s = j / (size_t)B; const int k = (int)(j % (size_t)B);
             char path[4096]; std::snprintf(path, sizeof path, cpat.c_str(), (unsigned)(starts[s0 + s] + k));
             std::string e;
-            const int r = read_png_raw(path, T->raws[s][(size_t)k], e, &scratch[wk], dev_inflate);
-            if (r == 1) present[s][(size_t)k] = 1;
+            // by signature, not by extension: a JPEG gives its coefficients (marker parse + Huffman decode), a PNG its scanlines.  A JPEG variant
+            // the rule refuses (r == 0) has no host fallback either: its segment fails with the feature's name
+            const bool jp = is_jpeg_file(path);
+            const double tj0 = jp ? now_ms() : 0;
+            int r = jp ? read_jpeg_raw(path, T->jraws[s][(size_t)k], e, &scratch[wk]) : read_png_raw(path, T->raws[s][(size_t)k], e, &scratch[wk], dev_inflate);
+            if (jp) { jpeg_us += (long)((now_ms() - tj0) * 1000.0); if (r == 0) r = -1; }
+            if (r == 1) { present[s][(size_t)k] = 1; (jp ? n_jpeg : n_png)++; }
             else if (r == 0) odd = 1;
             else if (k == 0 || starts[s0 + s] + k < cfg.ktx2_file_count) { std::lock_guard<std::mutex> l(mu); if (T->bad < 0 || (int)s < T->bad) { T->bad = (int)s; T->err = e; } }
           });
           bool ok = !odd && T->bad < 0 && T->ns > 0 && present[0][0];
+          T->jpeg = false;
+          if (ok && n_jpeg > 0) {                              // all JPEG of one size and one layout: the IDCT runs on the GPU; a batch that mixes kinds or layouts is decoded on the host
+            ok = n_png == 0;
+            if (ok) { const JpegRaw &r0 = T->jraws[0][0]; for (size_t s = 0; s < T->ns && ok; s++) for (size_t k = 0; k < (size_t)B && ok; k++) if (present[s][k]) { const JpegRaw &r = T->jraws[s][k]; ok = r.w == r0.w && r.h == r0.h && r.components == r0.components && r.luma_h == r0.luma_h && r.luma_v == r0.luma_v; } }
+            if (ok) {
+              T->dev = true; T->jpeg = true;
+              for (size_t s = 0; s < T->ns; s++) { size_t n = 0; while (n < (size_t)B && present[s][n]) n++; T->imgs[s].resize(n); for (size_t k = 0; k < n; k++) { T->imgs[s][k].w = T->jraws[s][k].w; T->imgs[s][k].h = T->jraws[s][k].h; } }
+              if (g_timing && T->ns) std::fprintf(stderr, "[uvolenc-timing] tex load  s0=%zu n=%zu segments %.0f ms (jpeg: marker parse + Huffman decode only, %d files, %.2f ms per file)\n", s0, T->ns, now_ms() - tl0, n_jpeg.load(), jpeg_us.load() / 1000.0 / std::max(1, n_jpeg.load()));
+              return T;
+            }
+          }
           if (ok) { const PngRaw &r0 = T->raws[0][0]; for (size_t s = 0; s < T->ns && ok; s++) for (size_t k = 0; k < (size_t)B && ok; k++) if (present[s][k]) { const PngRaw &r = T->raws[s][k]; ok = r.w == r0.w && r.h == r0.h && r.ch == r0.ch; } }
           if (ok) {
             T->dev = true;
@@ -392,7 +412,7 @@ int main(int argc, char **argv) {
           const size_t s = j / (size_t)B; const int k = (int)(j % (size_t)B);
           char path[4096]; std::snprintf(path, sizeof path, cpat.c_str(), (unsigned)(starts[s0 + s] + k));
           std::string e;
-          if (read_png(path, T->imgs[s][(size_t)k], e, &scratch[wk])) present[s][(size_t)k] = 1;
+          if (read_image(path, T->imgs[s][(size_t)k], e, &scratch[wk])) present[s][(size_t)k] = 1;      // PNG or JPEG, by signature
           else if (k == 0 || starts[s0 + s] + k < cfg.ktx2_file_count) { std::lock_guard<std::mutex> l(mu); if (T->bad < 0 || (int)s < T->bad) { T->bad = (int)s; T->err = e; } }
         });
         for (size_t s = 0; s < T->ns; s++) { size_t n = 0; while (n < (size_t)B && present[s][n]) n++; T->imgs[s].resize(n); }   // layers of a short last segment
@@ -407,11 +427,15 @@ int main(int argc, char **argv) {
       auto issue = [&](TexBatch &Tb) -> bool {
         Tb.issued = true; Tb.dptr.assign(Tb.ns, {});
         if (!Tb.dev || Tb.bad >= 0) return true;
-        std::vector<const uint8_t *> rp; for (size_t s = 0; s < Tb.ns; s++) for (size_t k = 0; k < Tb.imgs[s].size(); k++) rp.push_back(Tb.raws[s][k].raw.data());
-        std::vector<const uint8_t *> dp(rp.size(), nullptr);
+        std::vector<const uint8_t *> rp; if (!Tb.jpeg) for (size_t s = 0; s < Tb.ns; s++) for (size_t k = 0; k < Tb.imgs[s].size(); k++) rp.push_back(Tb.raws[s][k].raw.data());
+        std::vector<const int16_t *> jc; std::vector<const uint16_t *> jq;
+        if (Tb.jpeg) for (size_t s = 0; s < Tb.ns; s++) for (size_t k = 0; k < Tb.imgs[s].size(); k++) { jc.push_back(Tb.jraws[s][k].coef.data()); jq.push_back(Tb.jraws[s][k].qt.data()); }
+        std::vector<const uint8_t *> dp(Tb.jpeg ? jc.size() : rp.size(), nullptr);
         Tb.slot = (int)((n_issue++) & 1);
         int rcu;
-        if (dev_inflate) { std::vector<size_t> zl; for (size_t s = 0; s < Tb.ns; s++) for (size_t k = 0; k < Tb.imgs[s].size(); k++) zl.push_back(Tb.raws[s][k].raw.size());
+        if (Tb.jpeg) { const JpegRaw &r0 = Tb.jraws[0][0]; const uvol_jpeg_layout lay = { r0.w, r0.h, r0.components, r0.luma_h, r0.luma_v };
+          rcu = uvol_idct_jpeg_batch_dev(tctxs[g], jc.data(), jq.data(), (int)jc.size(), &lay, Tb.slot, dp.data()); }
+        else if (dev_inflate) { std::vector<size_t> zl; for (size_t s = 0; s < Tb.ns; s++) for (size_t k = 0; k < Tb.imgs[s].size(); k++) zl.push_back(Tb.raws[s][k].raw.size());
           rcu = uvol_inflate_png_batch_dev(tctxs[g], rp.data(), zl.data(), (int)rp.size(), Tb.raws[0][0].w, Tb.raws[0][0].h, Tb.raws[0][0].ch, Tb.slot, dp.data()); }
         else rcu = uvol_unfilter_png_batch_dev(tctxs[g], rp.data(), (int)rp.size(), Tb.raws[0][0].w, Tb.raws[0][0].h, Tb.raws[0][0].ch, Tb.slot, dp.data());
         if (rcu != UVOL_OK) { fail(starts[Tb.s0], uvol_last_error(tctxs[g])); return false; }
@@ -437,7 +461,7 @@ int main(int argc, char **argv) {
         for (auto &seg : T->imgs) for (auto &im : seg) if (im.w != w || im.h != h) same = false;
         if (!same) { fail(starts[s0], "image sizes differ"); break; }
         tex_w = w; tex_h = h;
-        if (T->dev && dev_inflate) {                   // a PNG whose zlib stream the device found corrupt: its segment fails as `basisu` would on that file (scripts/Encoder.py:293-298)
+        if (T->dev && dev_inflate && !T->jpeg) {                   // a PNG whose zlib stream the device found corrupt: its segment fails as `basisu` would on that file (scripts/Encoder.py:293-298)
           size_t ni = 0; for (auto &seg : T->imgs) ni += seg.size();
           std::vector<int> pst(ni, UVOL_OK); int bad_seg = -1;
           if (uvol_png_status(tctxs[g], T->slot, pst.data(), (int)ni) != UVOL_OK) { fail(starts[s0], uvol_last_error(tctxs[g])); break; }

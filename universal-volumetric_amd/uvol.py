@@ -72,7 +72,13 @@ EXPORTS = ["uvol_params_default", "uvol_abi_version", "uvol_device_count", "uvol
            "uvol_decode_mesh_batch_points", "uvol_decode_mesh_batch_packed", "uvol_downscale_rgba_batch_dev",
            "uvol_etc2_rgb_bound", "uvol_encode_etc2_rgb_batch",
            "uvol_mip_level_count", "uvol_mipchain_rgba_batch_dev", "uvol_texture_bound_mips", "uvol_encode_texture_segments_mips", "uvol_ktx2_levels",
-           "uvol_transcode_texture_segments_level"]
+           "uvol_transcode_texture_segments_level",
+           "uvol_jpeg_coeff_count", "uvol_idct_jpeg_batch_dev"]
+
+
+class JpegLayout(C.Structure):
+    """uvol_jpeg_layout: one layout for all images of a uvol_idct_jpeg_batch_dev call."""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("components", C.c_int), ("luma_h", C.c_int), ("luma_v", C.c_int)]
 
 
 def load(path=None):
@@ -140,6 +146,9 @@ def load(path=None):
                                                         C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
         L.uvol_ktx2_levels.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_uint32)]
         L.uvol_transcode_texture_segments_level.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(C.c_void_p), C.c_size_t, C.c_int, C.c_int, C.POINTER(C.c_int)]
+    if hasattr(L, "uvol_idct_jpeg_batch_dev"):      # (a build that predates the JPEG ingest still loads beside this one)
+        L.uvol_jpeg_coeff_count.argtypes = [C.POINTER(JpegLayout)]; L.uvol_jpeg_coeff_count.restype = C.c_size_t
+        L.uvol_idct_jpeg_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_int, C.POINTER(JpegLayout), C.c_int, C.POINTER(C.c_void_p)]
     L.uvol_parse_obj_batch_dev.argtypes = [C.c_void_p, C.POINTER(C.c_char_p), C.POINTER(C.c_size_t), C.c_int, C.c_int, C.POINTER(Mesh), C.POINTER(C.c_int)]
     L.uvol_encode_mesh_batch_dev_out.argtypes = [C.c_void_p, C.POINTER(Mesh), C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_int)]
     L.uvol_profile_enable.argtypes = [C.c_void_p, C.c_int]
@@ -342,6 +351,37 @@ class Codec:
         if sync and self.L.uvol_sync(self.h) != UVOL_OK:
             raise UvolError(f"uvol_sync: {self.error()}")
         return [int(p) for p in out], list(st)
+
+    def jpeg_coeff_count(self, width, height, components, luma_h=1, luma_v=1):
+        """uvol_jpeg_coeff_count: int16 values per image of that layout (0: a layout outside the rule)."""
+        lay = JpegLayout(width, height, components, luma_h, luma_v)
+        return int(self.L.uvol_jpeg_coeff_count(C.byref(lay)))
+
+    def idct_jpeg_batch_dev(self, coeffs, qtables, width, height, components, luma_h=1, luma_v=1, slot=0, sync=True):
+        """uvol_idct_jpeg_batch_dev: coeffs[i] = the quantised coefficients of image i (int16, uvol_jpeg_coeff_count values, the layout of
+        include/uvol_codec.h), qtables[i] = its components x 64 quantisation values (uint16) -> list of DEVICE pointers to the RGBA8 layers in the
+        ingest slot.  Arrays are passed where they lie (arrays of a PinnedArena are read without the staging copy); None stands for NULL.
+        sync=False: return once the kernels are queued (this context's texture entry points order themselves behind them)."""
+        n = len(coeffs if coeffs is not None else qtables); keep = []
+
+        def ptrs(items, dt):
+            out = []
+            for a in items:
+                if a is None:
+                    out.append(None); continue
+                if not (isinstance(a, np.ndarray) and a.dtype == dt and a.flags.c_contiguous):
+                    a = np.ascontiguousarray(a, dtype=dt)
+                keep.append(a); out.append(a.ctypes.data)
+            return (C.c_void_p * len(out))(*out)
+        cp = ptrs(coeffs, np.int16) if coeffs is not None else None
+        qp = ptrs(qtables, np.uint16) if qtables is not None else None
+        lay = JpegLayout(width, height, components, luma_h, luma_v); out = (C.c_void_p * max(n, 1))()
+        rc = self.L.uvol_idct_jpeg_batch_dev(self.h, cp, qp, n, C.byref(lay), slot, out)
+        if rc != UVOL_OK:
+            raise UvolError(f"idct_jpeg_batch_dev rc={rc}: {self.error()}")
+        if sync and self.L.uvol_sync(self.h) != UVOL_OK:
+            raise UvolError(f"uvol_sync: {self.error()}")
+        return [int(p) for p in out[:n]]
 
     def downscale_rgba_batch_dev(self, layers_or_ptrs, width, height, factor, slot=0, on_device=None):
         """uvol_downscale_rgba_batch_dev: layers of one size, downscaled by factor 2 / 4 / 8 on the device -> list of DEVICE pointers to the
