@@ -324,44 +324,61 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_sb_write(GeoJob *jobs) {
   }
 }
 
-// attribute vertices of the vertices an interior seam touches (grid z = attribute slot): pass a gives every segment (maximal
-// run of fan corners no seam / boundary separates) an id nverts_base + k at its left-most corner, pass b hands it to the other
-// corners of the segment.  Corners of untouched vertices keep their base vertex and are NOT written (att_vertex).
-__global__ void __launch_bounds__(UVOL_BLOCK) k_aseg_a(GeoJob *jobs) {
-  JOB_OR_RETURN;
-  const int i = (int)blockIdx.z;
-  if (i >= J.nad || !J.interior_seams[i]) return;
-  const uint32_t c0 = blockIdx.x * (UVOL_BLOCK * GEO_ILP) + threadIdx.x, nc = J.nc;
-  int32_t v[GEO_ILP]; uint32_t w[GEO_ILP];
-#pragma unroll
-  for (int k = 0; k < GEO_ILP; k++) { const uint32_t c = c0 + k * UVOL_BLOCK; v[k] = c < nc ? geo_vt(J)[c] : 0; }
-#pragma unroll
-  for (int k = 0; k < GEO_ILP; k++) w[k] = J.vseam[i][(uint32_t)v[k] >> 5];
-#pragma unroll
-  for (int k = 0; k < GEO_ILP; k++) {
-    const uint32_t c = c0 + k * UVOL_BLOCK;
-    if (c >= nc || !((w[k] >> ((uint32_t)v[k] & 31)) & 1u)) continue;
-    // left-most corner of its segment <=> the edge to its left is a seam or a boundary <=> the seam flag of corner next(c)
-    if (fseam_bit(J, i, g_nxt((int)c))) J.avert[i][c] = (int32_t)(J.nverts_t[0] + atomicAdd(&J.nseg[i], 1u));
+// One segment of a fan - a maximal run of corners that no seam / boundary separates - from its left-most corner c rightwards: every
+// corner of it takes the attribute vertex `id`.  copp(p) = the corner opposite p in the seam-cut table, < 0 across a seam / boundary
+// (the flag and the opposite corner are two independent loads: one memory round trip per step).  A closed fan with ONE seam edge is a
+// single segment that ends at the seam it started from.  False: more than nc steps (a fan that never ends: the flags are not symmetric
+// across some edge).  The callers hand in what they read through the job record as values: the stores to avert[] may alias the record
+// for all the compiler knows, and it would load the arrays' addresses again behind every one of them.
+template <typename CutOpp> __device__ __forceinline__ bool aseg_fill(int32_t *avert, int c, int32_t id, uint32_t nc, CutOpp copp) {
+  uint32_t guard = 0;
+  for (int a = c;;) {
+    avert[a] = id;
+    const int o = copp(g_prv(a));
+    if (o < 0) return true;
+    a = g_prv(o);
+    if (++guard > nc) return false;
   }
 }
-__global__ void __launch_bounds__(UVOL_BLOCK) k_aseg_b(GeoJob *jobs) {
+// attribute vertices of the vertices an interior seam touches, one thread per stored FACE, both attribute slots: the seam flags of the
+// face (k_seams: one byte, zero for the faces no seam or boundary borders) name the segments that start in it - corner c is the left-most
+// corner of its segment <=> the edge to its left is a seam or a boundary <=> the flag of corner next(c) is set.  The thread of that flag
+// gives the segment an id nverts_base + k and walks it (aseg_fill).  Every touched vertex has a flagged edge in its fan, the flags are
+// symmetric across an edge and swinging right inverts swinging left, so every corner of a touched vertex lies in exactly one segment and
+// is written exactly once.  Corners of untouched vertices keep their base vertex and are NOT written (att_vertex): a boundary edge sets
+// the flag but starts nothing there.  The size of the table's id space, nverts_t[2 + slot], is published by k_pack_tabs.
+// The kernel is a chain of dependent loads in few lanes of a wave, so the chain is kept short: the face's vertex triple is one load, the
+// 'touched' words of all flagged edges are fetched together, and a slot draws the ids of the face's segments with one atomic add.
+__global__ void __launch_bounds__(UVOL_BLOCK) k_aseg(GeoJob *jobs) {
   JOB_OR_RETURN;
-  const int i = (int)blockIdx.z;
-  if (i >= J.nad || !J.interior_seams[i]) return;
-  const uint32_t c0 = blockIdx.x * (UVOL_BLOCK * GEO_ILP) + threadIdx.x, nc = J.nc;
-  if (c0 == 0) { const uint32_t tot = J.nverts_t[0] + J.nseg[i]; J.nverts_t[2 + i] = tot; if (tot > J.ecap) J.status = GEO_E_WS_OVERFLOW; }
-  uint32_t v[GEO_ILP], w[GEO_ILP];
+  const uint32_t f = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (f >= J.nf) return;
+  const uint8_t *const fseam = J.fseam;
+  const uint32_t fs = fseam[f];
+  if (!fs) return;
+  const int32_t *const opp = J.opp;
+  const uint32_t nc = J.nc, nbase = J.nverts_t[0];
+  const uvol_s3 v3 = *reinterpret_cast<const uvol_s3 *>(geo_vt(J) + 3 * (size_t)f);
+  const uint32_t vv[3] = { (uint32_t)v3.x, (uint32_t)v3.y, (uint32_t)v3.z };
+  uint32_t live = 0, w[6];                                    // bit 3 i + k: flagged edge k of a slot that has interior seams
+  for (int i = 0; i < 2; i++) if (i < J.nad && J.interior_seams[i]) live |= fs & (7u << (3 * i));
 #pragma unroll
-  for (int k = 0; k < GEO_ILP; k++) { const uint32_t c = c0 + k * UVOL_BLOCK; v[k] = c < nc ? (uint32_t)geo_vt(J)[c] : 0u; }
+  for (int b = 0; b < 6; b++) { const uint32_t v = vv[(b % 3 + 2) % 3]; w[b] = ((live >> b) & 1u) ? J.vseam[b / 3][v >> 5] : 0u; }
+  uint32_t start = 0;                                         // ... whose left end - corner prev(3 f + k) - an interior seam touches
 #pragma unroll
-  for (int k = 0; k < GEO_ILP; k++) w[k] = J.vseam[i][v[k] >> 5];
-#pragma unroll
-  for (int k = 0; k < GEO_ILP; k++) {
-    const uint32_t c = c0 + k * UVOL_BLOCK;
-    if (c >= nc || !((w[k] >> (v[k] & 31)) & 1u)) continue;
-    int l = (int)c; uint32_t guard = 0;
-    for (;;) { const int nl = st_swl(J, i, l); if (nl < 0) break; l = nl; if (++guard > nc) { J.status = -22; return; } }
-    if (l != (int)c) J.avert[i][c] = J.avert[i][l];
+  for (int b = 0; b < 6; b++) start |= ((w[b] >> (vv[(b % 3 + 2) % 3] & 31)) & 1u) << b;
+  for (int i = 0; i < 2; i++) {
+    const uint32_t st = (start >> (3 * i)) & 7u;
+    if (!st) continue;
+    int32_t *const avert = J.avert[i];
+    int32_t id = (int32_t)(nbase + atomicAdd(&J.nseg[i], (uint32_t)__popc(st)));
+    const int sh = 3 * i;
+    for (int k = 0; k < 3; k++) {
+      if (!((st >> k) & 1u)) continue;
+      const bool ok = aseg_fill(avert, 3 * (int)f + (k + 2) % 3, id++, nc, [=](int p) {
+        const uint32_t fb = fseam[p / 3]; const int o = opp[p];
+        return ((fb >> (sh + p % 3)) & 1u) ? GEO_INV : o; });
+      if (!ok) { J.status = -22; return; }
+    }
   }
 }

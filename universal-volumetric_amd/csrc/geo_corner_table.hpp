@@ -181,7 +181,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_edge_match(GeoJob *jobs) {
 // (visited bitmaps, valences and entry maps are keyed by them), so ids may have holes (unused positions) and the extra ids of
 // non-manifold fans may be handed out in any order.
 // Table 1 (decoder-order base table) re-uses these ids through the corner renumbering; the attribute tables split only the
-// vertices an interior seam touches (k_aseg_a / k_aseg_b), every other vertex keeps its base id.
+// vertices an interior seam touches (k_aseg), every other vertex keeps its base id.
 // ------------------------------------------------------------------------------------------------
 // fan of corner c in table T: representative (left-most corner of an open fan, lowest corner of a closed one), size, open flag
 __device__ inline int fan_probe(const GTab &T, int c, int limit, int &cnt, bool &open) {

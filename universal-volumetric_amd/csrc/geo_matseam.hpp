@@ -18,7 +18,6 @@
 #define MS_LIVE(J) ((J).status == 0 && (J).ms.on && (J).mat_seam)
 __device__ __forceinline__ bool ms_fseam_bit(const GeoJob &J, int c) { return (J.ms.fseam[c / 3] >> (c % 3)) & 1u; }
 __device__ __forceinline__ int ms_opp(const GeoJob &J, int c) { return (c < 0 || ms_fseam_bit(J, c)) ? GEO_INV : J.opp[c]; }
-__device__ __forceinline__ int ms_swl(const GeoJob &J, int c) { const int o = ms_opp(J, g_nxt(c)); return o < 0 ? GEO_INV : g_nxt(o); }
 __device__ __forceinline__ bool ms_touched(const GeoJob &J, uint32_t v) { return (J.ms.vseam[v >> 5] >> (v & 31)) & 1u; }
 // vertex of corner c in the material's table: the base vertex unless a material seam touches it
 __device__ __forceinline__ int ms_vertex(const GeoJob &J, int c) { const int v = geo_vt(J)[c]; return ms_touched(J, (uint32_t)v) ? J.ms.avert[c] : v; }
@@ -92,22 +91,34 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_ms_sb_write(GeoJob *jobs) {
   if (threadIdx.x == 0 && zc) atomicAdd(&J.rb[GEO_RB_MAT].zeros, zc);
   if (blockIdx.x == 0 && threadIdx.x == 0) { J.rb[GEO_RB_MAT].n = J.bsum[uvol_blocks_dev(nf)]; J.rb[GEO_RB_MAT].bits = J.ms.sbits; }
 }
-// attribute vertices of the touched vertices (k_aseg_a / k_aseg_b's rule): every segment - maximal run of fan corners no seam or boundary
-// separates - gets an id nverts_base + k at its left-most corner, then the other corners of the segment take it
+// attribute vertices of the touched vertices (k_aseg's rule and its segment walk, aseg_fill).  Pass 0, one thread per stored face: every
+// flagged edge whose left end a material seam touches starts a segment - maximal run of fan corners no seam or boundary separates - which
+// gets an id nverts_base + k and is walked rightwards.  Pass 1, one thread per frame: the size of the table's vertex id space.
 __global__ void __launch_bounds__(UVOL_BLOCK) k_ms_aseg(GeoJob *jobs, int pass) {
   GeoJob &J = jobs[blockIdx.y];
   if (!MS_LIVE(J)) return;
-  const uint32_t c = blockIdx.x * UVOL_BLOCK + threadIdx.x, nc = J.nc;
-  if (pass == 1 && c == 0) { const uint32_t tot = J.nverts_t[0] + J.ms.nseg; J.ms.nverts = tot; if (tot > J.ecap) J.status = GEO_E_WS_OVERFLOW; }
-  if (c >= nc || !ms_touched(J, (uint32_t)geo_vt(J)[c])) return;
-  if (pass == 0) {
-    // left-most corner of its segment <=> the edge to its left is a seam or a boundary <=> the seam flag of corner next(c)
-    if (ms_fseam_bit(J, g_nxt((int)c))) J.ms.avert[c] = (int32_t)(J.nverts_t[0] + atomicAdd(&J.ms.nseg, 1u));
+  const uint32_t f = blockIdx.x * UVOL_BLOCK + threadIdx.x;
+  if (pass == 1) {
+    if (f == 0) { const uint32_t tot = J.nverts_t[0] + J.ms.nseg; J.ms.nverts = tot; if (tot > J.ecap) J.status = GEO_E_WS_OVERFLOW; }
     return;
   }
-  int l = (int)c; uint32_t guard = 0;
-  for (;;) { const int nl = ms_swl(J, l); if (nl < 0) break; l = nl; if (++guard > nc) { J.status = -22; return; } }
-  if (l != (int)c) J.ms.avert[c] = J.ms.avert[l];
+  if (f >= J.nf) return;
+  const uint8_t *const fseam = J.ms.fseam;
+  const uint32_t fs = fseam[f];
+  if (!fs) return;
+  const int32_t *const opp = J.opp, *const vt = geo_vt(J);
+  int32_t *const avert = J.ms.avert;
+  const uint32_t nc = J.nc, nbase = J.nverts_t[0];
+  for (int k = 0; k < 3; k++) {
+    if (!((fs >> k) & 1u)) continue;
+    const int c = g_prv(3 * (int)f + k);
+    if (!ms_touched(J, (uint32_t)vt[c])) continue;
+    const int32_t id = (int32_t)(nbase + atomicAdd(&J.ms.nseg, 1u));
+    const bool ok = aseg_fill(avert, c, id, nc, [=](int p) {
+      const uint32_t fb = fseam[p / 3]; const int o = opp[p];
+      return ((fb >> (p % 3)) & 1u) ? GEO_INV : o; });
+    if (!ok) { J.status = -22; return; }
+  }
 }
 // Records of the material's table for the serial traverser and what follows it, one thread per stored face: avert[] becomes, for EVERY
 // corner, attribute vertex << 1 | open (in place: a thread reads only the entries it writes), ropp[] the opposite corner through the

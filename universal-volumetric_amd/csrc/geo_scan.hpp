@@ -69,7 +69,7 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_scan_sums(GeoJob *jobs, int sel)
   if (threadIdx.x == 0) bsum[nblocks] = carry;
 }
 
-// Corners per thread in the per-corner gather kernels (k_edge_match, k_aseg_a/b): they are latency-bound at full occupancy, so a
+// Corners per thread in the per-corner gather kernels (k_edge_match): they are latency-bound at full occupancy, so a
 // thread issues every level of its dependent loads for GEO_ILP corners (one block stride apart: coalesced) before using any.
 #define GEO_ILP 4
 #endif      // GEO_SCAN_BLOCK_ONLY

@@ -91,6 +91,8 @@ __global__ void __launch_bounds__(UVOL_BLOCK) k_pack_tabs(GeoJob *jobs, int r8, 
   if (f == 0) pack_dummy_record(J.rec[which], J.nf, r8);
   const int ai = which >= 2 ? which - 2 : -1;
   const uint32_t nbase = J.nverts_t[0], fs = ai >= 0 ? (uint32_t)J.fseam[f] >> (3 * ai) : 0u;
+  // the size of an attribute table's id space: base vertices + the segments k_aseg handed out (nobody reads it before the traversals)
+  if (f == 0 && ai >= 0) { const uint32_t tot = nbase + J.nseg[ai]; J.nverts_t[which] = tot; if (tot > J.ecap) J.status = GEO_E_WS_OVERFLOW; }
   const uvol_s3 o3 = *reinterpret_cast<const uvol_s3 *>(J.opp + 3 * (size_t)f), v3 = *reinterpret_cast<const uvol_s3 *>(geo_vt(J) + 3 * (size_t)f);
   const int oo[3] = { o3.x, o3.y, o3.z }, vv[3] = { v3.x, v3.y, v3.z };
   int r[3], vc[3];

@@ -994,17 +994,17 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
     }
     UVOL_HIP_CHECK(ctx, hipEventRecord(L.ev_val, L.aux));
   }
-  // (Seam flags and attribute vertices - k_seams, k_aseg_a, k_aseg_b - read the stored tables only, not the walk's output, and were
-  // tried on the auxiliary stream BESIDE the walk: slower in both forms of the join, 2632 - 2691 against 2733 - 2765 frames/s early;
-  // the walk is the chain's latency-bound link and pays for streaming neighbours.  DESIGN section 5, "measured and not kept".)
+  // (Seam flags and attribute vertices - k_seams and, then, the two per-corner passes k_aseg_a / k_aseg_b that k_aseg replaced - read the
+  // stored tables only, not the walk's output, and were tried on the auxiliary stream BESIDE the walk: slower in both forms of the join,
+  // 2632 - 2691 against 2733 - 2765 frames/s early; the walk is the chain's latency-bound link and pays for streaming neighbours.
+  // DESIGN section 5, "measured and not kept".)
   {
     uvol_ctx::Scope sc(ctx, "geo.k4b_seams", 0);
     LAUNCH(k_seams, dim3(bf, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_sb_count, dim3(bf, N), dim3(UVOL_BLOCK), dj);
     LAUNCH(k_scan_sums, dim3(1, N), dim3(UVOL_BLOCK), dj, (int)SCAN_ELIG);
     LAUNCH(k_sb_write, dim3(bf, N), dim3(UVOL_BLOCK), dj);
-    LAUNCH(k_aseg_a, dim3(bci, N, 2), dim3(UVOL_BLOCK), dj);
-    LAUNCH(k_aseg_b, dim3(bci, N, 2), dim3(UVOL_BLOCK), dj);
+    LAUNCH(k_aseg, dim3(bf, N), dim3(UVOL_BLOCK), dj);
   }
   // Early join (a large call whose ring would not fit in device memory otherwise): the auxiliary stream is joined HERE, not behind the
   // traversals.  It then overlaps the renumber / seams group only (about as long), but everything it reads (old-order opposite corners and vertices, the symbol
@@ -1039,8 +1039,8 @@ static int geo_submit_impl(uvol_ctx *ctx, GeoLane &L, const uvol_mesh *meshes, i
       LAUNCH(k_ms_sb_count, dim3(bf, N), dim3(UVOL_BLOCK), dj);
       LAUNCH(k_scan_sums, dim3(1, N), dim3(UVOL_BLOCK), dj, (int)SCAN_ELIG);
       LAUNCH(k_ms_sb_write, dim3(bf, N), dim3(UVOL_BLOCK), dj);
-      LAUNCH(k_ms_aseg, dim3(bc, N), dim3(UVOL_BLOCK), dj, 0);
-      LAUNCH(k_ms_aseg, dim3(bc, N), dim3(UVOL_BLOCK), dj, 1);
+      LAUNCH(k_ms_aseg, dim3(bf, N), dim3(UVOL_BLOCK), dj, 0);
+      LAUNCH(k_ms_aseg, dim3(1, N), dim3(UVOL_BLOCK), dj, 1);
       LAUNCH(k_ms_pack, dim3(bf, N), dim3(UVOL_BLOCK), dj);
       LAUNCH(k_ms_traverse, dim3(N), dim3(64), dj);
       LAUNCH(k_ms_v2d, dim3(be, N), dim3(UVOL_BLOCK), dj);
