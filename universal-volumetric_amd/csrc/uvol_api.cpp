@@ -226,6 +226,55 @@ static void async_shutdown(uvol_ctx *ctx) {
   delete ctx->async; ctx->async = nullptr;
 }
 
+// ------------------------------------------------------------------------------------------------
+// Conventions that several entry points share
+// ------------------------------------------------------------------------------------------------
+// The batch entry points of the mesh codecs hand their frames on in consecutive groups of max_batch: run(b0, nb) is the group of nb frames
+// from frame b0; the first group that fails ends the call with its code
+static int for_groups(const uvol_ctx *ctx, size_t n, const std::function<int(size_t, int)> &run) {
+  const size_t mb = (size_t)ctx->prm.max_batch;
+  for (size_t b0 = 0; b0 < n; b0 += mb) {
+    const int rc = run(b0, (int)std::min(n - b0, mb));
+    if (rc != UVOL_OK) return rc;
+  }
+  return UVOL_OK;
+}
+
+// The render-ready forms (P = uvol_decoded_points / uvol_packed_points), after the entry point's own checks of its output pointers.
+// Foreign files and frames whose index array is too small fail in their own slot; the others go to the decoder (run = geo_decode_points /
+// geo_decode_packed) in groups of max_batch.  reset clears the output fields of a frame, which is all a frame that fails here reports -
+// but for n_faces of a frame that did not fit, the needed count.  Without a status array the call returns the last failing frame's code.
+template <class P>
+static int decode_welded(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, bool dev, P *out, int *status, void (*reset)(P &),
+                         int (*run)(uvol_ctx *, const uint8_t *const *, const size_t *, int, P *, int *, bool)) {
+  (void)hipSetDevice(ctx->device);
+  std::vector<int> sel; sel.reserve((size_t)n);
+  int worst = UVOL_OK;
+  for (int i = 0; i < n; i++) {
+    P &p = out[i]; reset(p);
+    uint32_t nf = 0, mv = 0; int st = UVOL_OK;
+    if (uvol_drc_info(drc[i], lens[i], &nf, &mv) != UVOL_OK) { st = UVOL_E_INVALID; ctx->set_error("frame %d: not a Draco 2.2 mesh", i); }
+    else if (p.cap_faces < nf) { st = UVOL_E_NOSPACE; p.n_faces = nf; ctx->set_error("frame %d: %u faces, capacity %u", i, nf, p.cap_faces); }
+    if (status) status[i] = st;
+    if (st == UVOL_OK) sel.push_back(i); else worst = st;
+  }
+  std::vector<const uint8_t *> f; std::vector<size_t> l; std::vector<P> p; std::vector<int> s;
+  const int rc = for_groups(ctx, sel.size(), [&](size_t b0, int nb) {
+    f.resize((size_t)nb); l.resize((size_t)nb); p.resize((size_t)nb); s.assign((size_t)nb, UVOL_OK);
+    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; f[(size_t)k] = drc[i]; l[(size_t)k] = lens[i]; p[(size_t)k] = out[i]; }
+    const int rg = run(ctx, f.data(), l.data(), nb, p.data(), s.data(), dev);
+    if (rg != UVOL_OK) return rg;
+    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; out[i] = p[(size_t)k]; if (status) status[i] = s[(size_t)k]; if (s[(size_t)k] != UVOL_OK) worst = s[(size_t)k]; }
+    return (int)UVOL_OK; });
+  if (rc != UVOL_OK) return rc;
+  return status ? UVOL_OK : worst;
+}
+static void reset_points(uvol_decoded_points &P) { P.n_faces = P.n_points = P.has_uv = P.has_nrm = 0; }
+static void reset_packed(uvol_packed_points &P) {
+  P.n_faces = P.n_points = P.has_uv = P.has_nrm = P.has_material = P.pos_bits = P.uv_bits = 0;
+  P.pos_min[0] = P.pos_min[1] = P.pos_min[2] = P.pos_scale = P.uv_min[0] = P.uv_min[1] = P.uv_scale = 0.0f;
+}
+
 extern "C" {
 
 void uvol_params_default(uvol_params *p) {
@@ -318,14 +367,9 @@ static int encode_batch_common(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bo
   { bool any = false; for (int i = 0; mats && i < n; i++) any = any || mats[i] != nullptr; if (!any) mats = nullptr; }
   // stock draco_encoder's sequential connectivity (level 0) codes every attribute per point: the material attribute is not built for it
   if (mats && ctx->prm.draco_compression_level == 0) { ctx->set_error("material ids with DRACO_COMPRESSION_LEVEL 0 (sequential connectivity) are not supported"); return UVOL_E_UNSUPPORTED; }
-  const int mb = ctx->prm.max_batch;
-  for (int b0 = 0; b0 < n; b0 += mb) {
-    const int nb = n - b0 < mb ? n - b0 : mb;
-    int rc = defer ? geo_encode_batch_begin(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, true, mats ? mats + b0 : nullptr, b0)
-                   : geo_encode_batch(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, mats ? mats + b0 : nullptr, b0);
-    if (rc != UVOL_OK) return rc;
-  }
-  return UVOL_OK;
+  return for_groups(ctx, (size_t)n, [&](size_t b0, int nb) {
+    return defer ? geo_encode_batch_begin(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, true, mats ? mats + b0 : nullptr, (int)b0)
+                 : geo_encode_batch(ctx, meshes + b0, nb, dev, outs + b0, caps + b0, out_lens + b0, status ? status + b0 : nullptr, mats ? mats + b0 : nullptr, (int)b0); });
 }
 
 int uvol_encode_mesh(uvol_ctx *ctx, const uvol_mesh *mesh, uint8_t *out, size_t cap, size_t *out_len) {
@@ -348,55 +392,56 @@ int uvol_encode_mesh_batch_dev(uvol_ctx *ctx, const uvol_mesh *meshes, int n, ui
   return encode_batch_common(ctx, meshes, n, true, outs, caps, out_lens, status);
 }
 
-int uvol_encode_texture_segment(uvol_ctx *ctx, const uint8_t *const *rgba, int n_layers, uint32_t width, uint32_t height,
-                                uint8_t *out, size_t cap, size_t *out_len) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !rgba || n_layers <= 0 || !out || !out_len || width == 0 || height == 0) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba, 1, n_layers, width, height, false, &out, &cap, out_len);
-  return tex_encode_segment(ctx, rgba, n_layers, width, height, false, out, cap, out_len);
+// The ETC1S-or-UASTC choice of every texture encode form.  status: the per-segment forms (nullptr: a failed segment fails the call).
+// defer: the enqueue form leaves its parts in flight for tex_flush, so that consecutive enqueued calls overlap on the device; only the
+// ETC1S encoder has such a form - the UASTC encoder completes its call, enqueued or not
+static int tex_encode_dispatch(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height, bool dev,
+                               uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status = nullptr, bool defer = false) {
+  if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba, n_segments, n_layers, width, height, dev, outs, caps, out_lens, status);
+  return tex_encode_segments(ctx, rgba, n_segments, n_layers, width, height, dev, outs, caps, out_lens, status, defer);
 }
-
-int uvol_encode_texture_segment_dev(uvol_ctx *ctx, const uint8_t *const *rgba_dev, int n_layers, uint32_t width, uint32_t height,
-                                    uint8_t *out, size_t cap, size_t *out_len) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !rgba_dev || n_layers <= 0 || !out || !out_len || width == 0 || height == 0) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba_dev, 1, n_layers, width, height, true, &out, &cap, out_len);
-  return tex_encode_segment(ctx, rgba_dev, n_layers, width, height, true, out, cap, out_len);
-}
-
-int uvol_encode_texture_segments(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height,
-                                 uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+// the four blocking forms without per-segment statuses
+static int tex_encode_entry(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height, bool dev,
+                            uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
   UVOL_AFTER_ASYNC(ctx);
   if (!ctx || !rgba || n_segments <= 0 || n_layers <= 0 || !outs || !caps || !out_lens || width == 0 || height == 0) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
-  if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba, n_segments, n_layers, width, height, false, outs, caps, out_lens);
-  return tex_encode_segments(ctx, rgba, n_segments, n_layers, width, height, false, outs, caps, out_lens);
+  return tex_encode_dispatch(ctx, rgba, n_segments, n_layers, width, height, dev, outs, caps, out_lens);
+}
+int uvol_encode_texture_segment(uvol_ctx *ctx, const uint8_t *const *rgba, int n_layers, uint32_t width, uint32_t height,
+                                uint8_t *out, size_t cap, size_t *out_len) {
+  return tex_encode_entry(ctx, rgba, 1, n_layers, width, height, false, out ? &out : nullptr, &cap, out_len);      // (a segment is a batch of one)
+}
+int uvol_encode_texture_segment_dev(uvol_ctx *ctx, const uint8_t *const *rgba_dev, int n_layers, uint32_t width, uint32_t height,
+                                    uint8_t *out, size_t cap, size_t *out_len) {
+  return tex_encode_entry(ctx, rgba_dev, 1, n_layers, width, height, true, out ? &out : nullptr, &cap, out_len);
+}
+int uvol_encode_texture_segments(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height,
+                                 uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
+  return tex_encode_entry(ctx, rgba, n_segments, n_layers, width, height, false, outs, caps, out_lens);
 }
 int uvol_encode_texture_segments_dev(uvol_ctx *ctx, const uint8_t *const *rgba_dev, int n_segments, int n_layers, uint32_t width, uint32_t height,
                                      uint8_t *const *outs, const size_t *caps, size_t *out_lens) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !rgba_dev || n_segments <= 0 || n_layers <= 0 || !outs || !caps || !out_lens || width == 0 || height == 0) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba_dev, n_segments, n_layers, width, height, true, outs, caps, out_lens);
-  return tex_encode_segments(ctx, rgba_dev, n_segments, n_layers, width, height, true, outs, caps, out_lens);
+  return tex_encode_entry(ctx, rgba_dev, n_segments, n_layers, width, height, true, outs, caps, out_lens);
 }
 
 // ---- enqueue forms (see the block comment above async_worker) ----
-static int mesh_batch_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n, bool dev, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
+// face_material: the parallel array of the _mat form (nullptr: none; kept as an empty vector and handed on as nullptr)
+static int mesh_batch_async(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, bool dev,
+                            uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
   if (!ctx || !meshes || n < 0 || !outs || !caps || !out_lens) return UVOL_E_INVALID;
   try {
     std::vector<uvol_mesh> m(meshes, meshes + n); std::vector<uint8_t *> o(outs, outs + n); std::vector<size_t> c(caps, caps + n);
-    return async_push(ctx, [ctx, m = std::move(m), o = std::move(o), c = std::move(c), n, dev, out_lens, status]() {
-      return encode_batch_common(ctx, m.data(), n, dev, o.data(), c.data(), out_lens, status, true); });
+    std::vector<const uint8_t *> fm; if (face_material) fm.assign(face_material, face_material + n);
+    return async_push(ctx, [ctx, m = std::move(m), o = std::move(o), c = std::move(c), fm = std::move(fm), n, dev, out_lens, status]() {
+      return encode_batch_common(ctx, m.data(), n, dev, o.data(), c.data(), out_lens, status, true, fm.empty() ? nullptr : fm.data()); });
   } catch (...) { ctx->set_error("enqueue: out of memory on the host"); return UVOL_E_HIP; }
 }
 int uvol_encode_mesh_batch_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
-  return mesh_batch_async(ctx, meshes, n, false, outs, caps, out_lens, status);
+  return mesh_batch_async(ctx, meshes, nullptr, n, false, outs, caps, out_lens, status);
 }
 int uvol_encode_mesh_batch_dev_async(uvol_ctx *ctx, const uvol_mesh *meshes, int n, uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
-  return mesh_batch_async(ctx, meshes, n, true, outs, caps, out_lens, status);
+  return mesh_batch_async(ctx, meshes, nullptr, n, true, outs, caps, out_lens, status);
 }
 // ---- material ids (GENERIC uint8 attribute): the batch entry points with one more parallel array ----
 int uvol_encode_mesh_batch_mat(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, int inputs_on_device,
@@ -406,29 +451,22 @@ int uvol_encode_mesh_batch_mat(uvol_ctx *ctx, const uvol_mesh *meshes, const uin
 }
 int uvol_encode_mesh_batch_mat_async(uvol_ctx *ctx, const uvol_mesh *meshes, const uint8_t *const *face_material, int n, int inputs_on_device,
                                      uint8_t *const *outs, const size_t *caps, size_t *out_lens, int *status) {
-  if (!face_material) return mesh_batch_async(ctx, meshes, n, inputs_on_device != 0, outs, caps, out_lens, status);
-  if (!ctx || !meshes || n < 0 || !outs || !caps || !out_lens) return UVOL_E_INVALID;
-  const bool dev = inputs_on_device != 0;
-  try {
-    std::vector<uvol_mesh> m(meshes, meshes + n); std::vector<uint8_t *> o(outs, outs + n); std::vector<size_t> c(caps, caps + n);
-    std::vector<const uint8_t *> fm(face_material, face_material + n);
-    return async_push(ctx, [ctx, m = std::move(m), o = std::move(o), c = std::move(c), fm = std::move(fm), n, dev, out_lens, status]() {
-      return encode_batch_common(ctx, m.data(), n, dev, o.data(), c.data(), out_lens, status, true, fm.data()); });
-  } catch (...) { ctx->set_error("enqueue: out of memory on the host"); return UVOL_E_HIP; }
+  return mesh_batch_async(ctx, meshes, face_material, n, inputs_on_device != 0, outs, caps, out_lens, status);
 }
 int uvol_decode_mesh_batch_mat(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                uvol_decoded_mesh *out, uint8_t *const *face_material, int *has_material, int *status) {
   UVOL_AFTER_ASYNC(ctx);
   if (!ctx || !drc || !lens || n < 0 || !out) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
-  const int mb = ctx->prm.max_batch;
-  for (int b0 = 0; b0 < n; b0 += mb) {
-    const int nb = n - b0 < mb ? n - b0 : mb;
-    const int rc = geo_decode_batch(ctx, drc + b0, lens + b0, nb, out + b0, status ? status + b0 : nullptr, outputs_on_device != 0,
-                                    face_material ? face_material + b0 : nullptr, has_material ? has_material + b0 : nullptr);
-    if (rc != UVOL_OK) return rc;
-  }
-  return UVOL_OK;
+  return for_groups(ctx, (size_t)n, [&](size_t b0, int nb) {
+    return geo_decode_batch(ctx, drc + b0, lens + b0, nb, out + b0, status ? status + b0 : nullptr, outputs_on_device != 0,
+                            face_material ? face_material + b0 : nullptr, has_material ? has_material + b0 : nullptr); });
+}
+int uvol_decode_mesh_batch(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, uvol_decoded_mesh *out, int *status) {
+  return uvol_decode_mesh_batch_mat(ctx, drc, lens, n, 0, out, nullptr, nullptr, status);
+}
+int uvol_decode_mesh_batch_dev(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, uvol_decoded_mesh *out, int *status) {
+  return uvol_decode_mesh_batch_mat(ctx, drc, lens, n, 1, out, nullptr, nullptr, status);
 }
 int uvol_decode_mesh_batch_points(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                   uvol_decoded_points *out, int *status) {
@@ -438,29 +476,7 @@ int uvol_decode_mesh_batch_points(uvol_ctx *ctx, const uint8_t *const *drc, cons
     if (out[i].layout != UVOL_POINTS_PLANAR && out[i].layout != UVOL_POINTS_INTERLEAVED) { ctx->set_error("frame %d: unknown point layout %u", i, out[i].layout); return UVOL_E_INVALID; }
     if (outputs_on_device && out[i].layout == UVOL_POINTS_INTERLEAVED && ((uintptr_t)out[i].pos & 15)) { ctx->set_error("frame %d: the interleaved device buffer must be 16-byte aligned", i); return UVOL_E_INVALID; }      // (host outputs are staged and copied)
   }
-  (void)hipSetDevice(ctx->device);
-  // foreign files and frames whose index array is too small fail in their own slot; the others go to the decoder in groups of max_batch
-  std::vector<int> sel; sel.reserve((size_t)n);
-  int worst = UVOL_OK;
-  for (int i = 0; i < n; i++) {
-    uvol_decoded_points &P = out[i]; P.n_faces = P.n_points = P.has_uv = P.has_nrm = 0;
-    uint32_t nf = 0, mv = 0; int st = UVOL_OK;
-    if (uvol_drc_info(drc[i], lens[i], &nf, &mv) != UVOL_OK) { st = UVOL_E_INVALID; ctx->set_error("frame %d: not a Draco 2.2 mesh", i); }
-    else if (P.cap_faces < nf) { st = UVOL_E_NOSPACE; P.n_faces = nf; ctx->set_error("frame %d: %u faces, capacity %u", i, nf, P.cap_faces); }
-    if (status) status[i] = st;
-    if (st == UVOL_OK) sel.push_back(i); else worst = st;
-  }
-  const int mb = ctx->prm.max_batch;
-  std::vector<const uint8_t *> f; std::vector<size_t> l; std::vector<uvol_decoded_points> p; std::vector<int> s;
-  for (size_t b0 = 0; b0 < sel.size(); b0 += (size_t)mb) {
-    const int nb = (int)std::min(sel.size() - b0, (size_t)mb);
-    f.resize((size_t)nb); l.resize((size_t)nb); p.resize((size_t)nb); s.assign((size_t)nb, UVOL_OK);
-    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; f[(size_t)k] = drc[i]; l[(size_t)k] = lens[i]; p[(size_t)k] = out[i]; }
-    const int rc = geo_decode_points(ctx, f.data(), l.data(), nb, p.data(), s.data(), outputs_on_device != 0);
-    if (rc != UVOL_OK) return rc;
-    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; out[i] = p[(size_t)k]; if (status) status[i] = s[(size_t)k]; if (s[(size_t)k] != UVOL_OK) worst = s[(size_t)k]; }
-  }
-  return status ? UVOL_OK : worst;
+  return decode_welded(ctx, drc, lens, n, outputs_on_device != 0, out, status, reset_points, geo_decode_points);
 }
 int uvol_decode_mesh_batch_packed(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, int outputs_on_device,
                                   uvol_packed_points *out, int *status) {
@@ -468,31 +484,7 @@ int uvol_decode_mesh_batch_packed(uvol_ctx *ctx, const uint8_t *const *drc, cons
   if (!ctx || !drc || !lens || n < 0 || !out) return UVOL_E_INVALID;
   for (int i = 0; i < n; i++)
     if (outputs_on_device && ((uintptr_t)out[i].records & 15)) { ctx->set_error("frame %d: the device records buffer must be 16-byte aligned", i); return UVOL_E_INVALID; }      // (host outputs are staged and copied)
-  (void)hipSetDevice(ctx->device);
-  // foreign files and frames whose index array is too small fail in their own slot; the others go to the decoder in groups of max_batch
-  std::vector<int> sel; sel.reserve((size_t)n);
-  int worst = UVOL_OK;
-  for (int i = 0; i < n; i++) {
-    uvol_packed_points &P = out[i];
-    P.n_faces = P.n_points = P.has_uv = P.has_nrm = P.has_material = P.pos_bits = P.uv_bits = 0;
-    P.pos_min[0] = P.pos_min[1] = P.pos_min[2] = P.pos_scale = P.uv_min[0] = P.uv_min[1] = P.uv_scale = 0.0f;
-    uint32_t nf = 0, mv = 0; int st = UVOL_OK;
-    if (uvol_drc_info(drc[i], lens[i], &nf, &mv) != UVOL_OK) { st = UVOL_E_INVALID; ctx->set_error("frame %d: not a Draco 2.2 mesh", i); }
-    else if (P.cap_faces < nf) { st = UVOL_E_NOSPACE; P.n_faces = nf; ctx->set_error("frame %d: %u faces, capacity %u", i, nf, P.cap_faces); }
-    if (status) status[i] = st;
-    if (st == UVOL_OK) sel.push_back(i); else worst = st;
-  }
-  const int mb = ctx->prm.max_batch;
-  std::vector<const uint8_t *> f; std::vector<size_t> l; std::vector<uvol_packed_points> p; std::vector<int> s;
-  for (size_t b0 = 0; b0 < sel.size(); b0 += (size_t)mb) {
-    const int nb = (int)std::min(sel.size() - b0, (size_t)mb);
-    f.resize((size_t)nb); l.resize((size_t)nb); p.resize((size_t)nb); s.assign((size_t)nb, UVOL_OK);
-    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; f[(size_t)k] = drc[i]; l[(size_t)k] = lens[i]; p[(size_t)k] = out[i]; }
-    const int rc = geo_decode_packed(ctx, f.data(), l.data(), nb, p.data(), s.data(), outputs_on_device != 0);
-    if (rc != UVOL_OK) return rc;
-    for (int k = 0; k < nb; k++) { const int i = sel[b0 + (size_t)k]; out[i] = p[(size_t)k]; if (status) status[i] = s[(size_t)k]; if (s[(size_t)k] != UVOL_OK) worst = s[(size_t)k]; }
-  }
-  return status ? UVOL_OK : worst;
+  return decode_welded(ctx, drc, lens, n, outputs_on_device != 0, out, status, reset_packed, geo_decode_packed);
 }
 int uvol_parse_obj_batch_dev_mat(uvol_ctx *ctx, const uint8_t *const *obj_text, const size_t *lens, int n, int slot, uvol_mesh *meshes_out,
                                  const uint8_t **face_material_dev_out, int *status) {
@@ -508,8 +500,7 @@ static int tex_segments_async(uvol_ctx *ctx, const uint8_t *const *rgba, int n_s
     std::vector<const uint8_t *> r(rgba, rgba + (size_t)n_segments * n_layers); std::vector<uint8_t *> o(outs, outs + n_segments); std::vector<size_t> c(caps, caps + n_segments);
     return async_push(ctx, [ctx, r = std::move(r), o = std::move(o), c = std::move(c), n_segments, n_layers, width, height, dev, out_lens]() {
       (void)hipSetDevice(ctx->device);
-      if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, r.data(), n_segments, n_layers, width, height, dev, o.data(), c.data(), out_lens);
-      return tex_encode_segments(ctx, r.data(), n_segments, n_layers, width, height, dev, o.data(), c.data(), out_lens, nullptr, true); });
+      return tex_encode_dispatch(ctx, r.data(), n_segments, n_layers, width, height, dev, o.data(), c.data(), out_lens, nullptr, true); });
   } catch (...) { ctx->set_error("enqueue: out of memory on the host"); return UVOL_E_HIP; }
 }
 int uvol_encode_texture_segments_async(uvol_ctx *ctx, const uint8_t *const *rgba, int n_segments, int n_layers, uint32_t width, uint32_t height,
@@ -534,7 +525,7 @@ static int decode_dispatch(uvol_ctx *ctx, const uint8_t *const *ktx2_in, const s
     if (target < 0 || target > UVOL_TARGET_BC3) { ctx->set_error("unknown transcode target"); return UVOL_E_UNSUPPORTED; }      // (UASTC sources take every target since round 5)
     return tex_uastc_decode_segments(ctx, ktx2, lens, n, out, layer_cap, dev, target);
   }
-  if (target == 3) { ctx->set_error("ASTC 4x4 is the transcode target of UASTC sources (KTX2Loader.js:591-600); this file is ETC1S"); return UVOL_E_UNSUPPORTED; }
+  if (target == UVOL_TARGET_ASTC) { ctx->set_error("ASTC 4x4 is the transcode target of UASTC sources (KTX2Loader.js:591-600); this file is ETC1S"); return UVOL_E_UNSUPPORTED; }
   return tex_decode_segments(ctx, ktx2, lens, n, out, layer_cap, dev, target);
 }
 // Per-segment results and mixed batches (reference scripts/Encoder.py:293-298 fails one basisu process, not the run; SURVEY 5
@@ -627,10 +618,7 @@ int uvol_encode_texture_segments_mips(uvol_ctx *ctx, const uint8_t *const *rgba,
       if (inputs_on_device && ((uintptr_t)rgba[i] & 3)) { ctx->set_error("uvol_encode_texture_segments_mips: rgba[%d] is a device layer that is not 4-byte aligned", i); return UVOL_E_INVALID; }
     }
   }
-  if (nl == 1) {
-    if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
-    return tex_encode_segments(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
-  }
+  if (nl == 1) return tex_encode_dispatch(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
   return tex_uastc_encode_segments_mips(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, nl, outs, caps, out_lens, status);
 }
 int uvol_ktx2_levels(const uint8_t *ktx2, size_t len, uint32_t *levels) {
@@ -647,74 +635,32 @@ int uvol_encode_texture_segments_st(uvol_ctx *ctx, const uint8_t *const *rgba, i
   if (!ctx || !rgba || n_segments <= 0 || n_layers < 1 || !outs || !caps || !out_lens || !status) return UVOL_E_INVALID;
   (void)hipSetDevice(ctx->device);
   for (int s = 0; s < n_segments; s++) { status[s] = UVOL_OK; out_lens[s] = 0; }
-  if (ctx->prm.uastc) return tex_uastc_encode_segments(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
-  return tex_encode_segments(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
+  return tex_encode_dispatch(ctx, rgba, n_segments, n_layers, width, height, inputs_on_device != 0, outs, caps, out_lens, status);
+}
+// the two decode and the four single-target transcode entry points
+static int decode_entry(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *out, size_t layer_cap, bool dev, int target) {
+  UVOL_AFTER_ASYNC(ctx);
+  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !out) return UVOL_E_INVALID;
+  (void)hipSetDevice(ctx->device);
+  return decode_dispatch(ctx, ktx2, lens, n_segments, out, layer_cap, dev, target);
 }
 int uvol_decode_texture_segments(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *rgba, size_t layer_cap) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !rgba) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  return decode_dispatch(ctx, ktx2, lens, n_segments, rgba, layer_cap, false, 0);
+  return decode_entry(ctx, ktx2, lens, n_segments, rgba, layer_cap, false, UVOL_TARGET_RGBA32);
 }
 int uvol_decode_texture_segments_dev(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *rgba_dev, size_t layer_cap) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !rgba_dev) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  return decode_dispatch(ctx, ktx2, lens, n_segments, rgba_dev, layer_cap, true, 0);
+  return decode_entry(ctx, ktx2, lens, n_segments, rgba_dev, layer_cap, true, UVOL_TARGET_RGBA32);
 }
 int uvol_transcode_texture_segments_etc1(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *blocks, size_t layer_cap, int outputs_on_device) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !blocks) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  return decode_dispatch(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, 1);
+  return decode_entry(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, UVOL_TARGET_ETC1);
 }
-
 int uvol_transcode_texture_segments_bc7(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *blocks, size_t layer_cap, int outputs_on_device) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !blocks) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  return decode_dispatch(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, 2);
+  return decode_entry(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, UVOL_TARGET_BC7);
 }
-
 int uvol_transcode_texture_segments_etc2_rgba(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *blocks, size_t layer_cap, int outputs_on_device) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !blocks) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  return decode_dispatch(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, 4);
+  return decode_entry(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, UVOL_TARGET_ETC2_RGBA);
 }
-
 int uvol_transcode_texture_segments_astc(uvol_ctx *ctx, const uint8_t *const *ktx2, const size_t *lens, int n_segments, uint8_t *const *blocks, size_t layer_cap, int outputs_on_device) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !ktx2 || !lens || n_segments <= 0 || !blocks) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  return decode_dispatch(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, 3);
-}
-
-int uvol_decode_mesh_batch(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, uvol_decoded_mesh *out, int *status) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !drc || !lens || n < 0 || !out) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  const int mb = ctx->prm.max_batch;
-  for (int b0 = 0; b0 < n; b0 += mb) {
-    const int nb = n - b0 < mb ? n - b0 : mb;
-    const int rc = geo_decode_batch(ctx, drc + b0, lens + b0, nb, out + b0, status ? status + b0 : nullptr);
-    if (rc != UVOL_OK) return rc;
-  }
-  return UVOL_OK;
-}
-
-// (the profile entry points wait for enqueued work first: the worker thread updates the same records)
-int uvol_decode_mesh_batch_dev(uvol_ctx *ctx, const uint8_t *const *drc, const size_t *lens, int n, uvol_decoded_mesh *out, int *status) {
-  UVOL_AFTER_ASYNC(ctx);
-  if (!ctx || !drc || !lens || n < 0 || !out) return UVOL_E_INVALID;
-  (void)hipSetDevice(ctx->device);
-  const int mb = ctx->prm.max_batch;
-  for (int b0 = 0; b0 < n; b0 += mb) {
-    const int nb = n - b0 < mb ? n - b0 : mb;
-    const int rc = geo_decode_batch(ctx, drc + b0, lens + b0, nb, out + b0, status ? status + b0 : nullptr, true);
-    if (rc != UVOL_OK) return rc;
-  }
-  return UVOL_OK;
+  return decode_entry(ctx, ktx2, lens, n_segments, blocks, layer_cap, outputs_on_device != 0, UVOL_TARGET_ASTC);
 }
 
 // (like every entry point it waits for this context's enqueued calls first: the worker thread and this call both borrow ctx->stream.  To
@@ -782,6 +728,7 @@ int uvol_encode_mesh_batch_dev_out(uvol_ctx *ctx, const uvol_mesh *meshes, int n
   return geo_encode_batch_dev_out(ctx, meshes, n, (hipStream_t)producer_stream, dev_out, dev_cap, out_offs, out_lens, status);
 }
 
+// (the profile entry points wait for enqueued work first: the worker thread updates the same records)
 int uvol_profile_enable(uvol_ctx *ctx, int on) { if (!ctx) return UVOL_E_INVALID; UVOL_AFTER_ASYNC(ctx); ctx->profiling = on != 0; return UVOL_OK; }
 int uvol_profile_reset(uvol_ctx *ctx) {
   if (!ctx) return UVOL_E_INVALID;

@@ -205,6 +205,43 @@ def _u32(a):
     return None if a is None else np.ascontiguousarray(a, dtype=np.uint32).reshape(-1)
 
 
+def _files(files):
+    """The file-list arguments of the ABI -> (the files as bytes, the char* array, the length array, their count)."""
+    files = [bytes(f) for f in files]; n = len(files)
+    return files, (C.c_char_p * n)(*files), (C.c_size_t * n)(*[len(f) for f in files]), n
+
+
+def _layers(items, width, height, on_device):
+    """The RGBA-layer intake of the batch calls on layers of one size: device pointers (ints), or host images (HxWx4 uint8 arrays / bytes of
+    width * height * 4), which the library uploads.  on_device=None: device pointers when every entry is an int.
+    -> (the void* array, the host arrays it points into, on_device)"""
+    items = list(items); n = len(items)
+    if on_device is None:
+        on_device = n > 0 and all(isinstance(x, int) for x in items)
+    if on_device:
+        return (C.c_void_p * n)(*[int(p) if p else None for p in items]), [], True
+    keep = []
+    for a in items:
+        if a is None:
+            keep.append(None); continue
+        a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
+        if a.size != width * height * 4:
+            raise ValueError("every layer must hold width * height * 4 bytes")
+        keep.append(a)
+    return (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep]), keep, False
+
+
+def _segments(segments):
+    """Host texture segments (lists of HxWx4 uint8 arrays, one size, one layer count) -> (the arrays in one list, their void* array, width,
+    height, layers per segment, segments)."""
+    arrs = [[np.ascontiguousarray(a, dtype=np.uint8) for a in seg] for seg in segments]
+    h, w = arrs[0][0].shape[:2]; nl = len(arrs[0])
+    flat = [a for seg in arrs for a in seg]
+    if any(len(seg) != nl for seg in arrs) or any(a.shape != (h, w, 4) for a in flat):
+        raise ValueError("all segments must have the same layer count and HxWx4 size")
+    return flat, (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat]), w, h, nl, len(arrs)
+
+
 class Codec:
     """One codec context = one GPU + one HIP stream.  Field names follow project-config.json."""
 
@@ -309,8 +346,7 @@ class Codec:
     def decode_mesh_batch_dev(self, files, metas):
         """files: list of .drc bytes; metas: ctypes array of DecodedMesh whose buffers are DEVICE pointers (capacities filled in by the
         caller, see uvol_drc_info): the decoded arrays stay in HBM, the counts come back in `metas`.  -> list of statuses."""
-        files = [bytes(f) for f in files]; n = len(files)
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
+        files, fp, ln, n = _files(files); st = (C.c_int * n)()
         rc = self.L.uvol_decode_mesh_batch_dev(self.h, fp, ln, n, metas, st)
         if rc != UVOL_OK:
             raise UvolError(f"decode_mesh_batch_dev rc={rc}: {self.error()}")
@@ -318,8 +354,7 @@ class Codec:
 
     def parse_obj_batch_dev(self, texts, slot=0):
         """texts: list of OBJ files as bytes -> (ctypes array of Mesh with DEVICE pointers into the context's slot, list of statuses)."""
-        texts = [bytes(t) for t in texts]; n = len(texts)
-        tp = (C.c_char_p * n)(*texts); ln = (C.c_size_t * n)(*[len(t) for t in texts]); meshes = (Mesh * n)(); st = (C.c_int * n)()
+        texts, tp, ln, n = _files(texts); meshes = (Mesh * n)(); st = (C.c_int * n)()
         rc = self.L.uvol_parse_obj_batch_dev(self.h, tp, ln, n, slot, meshes, st)
         if rc != UVOL_OK:
             raise UvolError(f"parse_obj_batch_dev rc={rc}: {self.error()}")
@@ -328,8 +363,7 @@ class Codec:
     def unfilter_png_batch_dev(self, inflated, width, height, channels, slot=0, sync=True):
         """inflated: list of bytes (the inflated IDAT stream of 8-bit RGB / RGBA PNGs of one size) -> list of DEVICE pointers to RGBA8 layers.
         sync=False: return once the kernel is queued (this context's texture entry points order themselves behind it)."""
-        raws = [bytes(r) for r in inflated]; n = len(raws)
-        rp = (C.c_char_p * n)(*raws); out = (C.c_void_p * n)()
+        raws, rp, _, n = _files(inflated); out = (C.c_void_p * n)()
         rc = self.L.uvol_unfilter_png_batch_dev(self.h, rp, n, width, height, channels, slot, out)
         if rc != UVOL_OK:
             raise UvolError(f"unfilter_png_batch_dev rc={rc}: {self.error()}")
@@ -340,8 +374,7 @@ class Codec:
     def inflate_png_batch_dev(self, zstreams, width, height, channels, slot=0, sync=True):
         """zstreams: list of bytes (the zlib stream = concatenated IDAT data of 8-bit RGB / RGBA PNGs of one size) -> (list of DEVICE pointers
         to RGBA8 layers, list of per-image statuses); inflate and un-filter both run on the device."""
-        zs = [bytes(z) for z in zstreams]; n = len(zs)
-        zp = (C.c_char_p * n)(*zs); ln = (C.c_size_t * n)(*[len(z) for z in zs]); out = (C.c_void_p * n)(); st = (C.c_int * n)()
+        zs, zp, ln, n = _files(zstreams); out = (C.c_void_p * n)(); st = (C.c_int * n)()
         rc = self.L.uvol_inflate_png_batch_dev(self.h, zp, ln, n, width, height, channels, slot, out)
         if rc != UVOL_OK:
             raise UvolError(f"inflate_png_batch_dev rc={rc}: {self.error()}")
@@ -388,21 +421,7 @@ class Codec:
         ceil(width / factor) x ceil(height / factor) RGBA8 layers in the context's downscale slot (valid until that slot is written again;
         what encode_texture_segment[s]_dev takes).  layers_or_ptrs: device pointers (ints), or host images (HxWx4 uint8 arrays / bytes of
         width * height * 4), which are uploaded.  on_device=None: device pointers when every entry is an int."""
-        items = list(layers_or_ptrs); n = len(items)
-        if on_device is None:
-            on_device = n > 0 and all(isinstance(x, int) for x in items)
-        keep = []
-        if on_device:
-            ptrs = (C.c_void_p * n)(*[int(p) if p else None for p in items])
-        else:
-            for a in items:
-                if a is None:
-                    keep.append(None); continue
-                a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
-                if a.size != width * height * 4:
-                    raise ValueError("every layer must hold width * height * 4 bytes")
-                keep.append(a)
-            ptrs = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep])
+        ptrs, keep, on_device = _layers(layers_or_ptrs, width, height, on_device); n = len(ptrs)
         out = (C.c_void_p * n)()
         rc = self.L.uvol_downscale_rgba_batch_dev(self.h, ptrs, n, width, height, 1 if on_device else 0, factor, slot, out)
         if rc != UVOL_OK:
@@ -417,21 +436,7 @@ class Codec:
         """uvol_mipchain_rgba_batch_dev: layers of one size -> their mip levels 1 .. levels - 1 (levels=0: the full chain), made on the device in
         one pass over level 0.  Returns one list per layer of DEVICE pointers, entry v - 1 = level v (max(1, width >> v) x max(1, height >> v)
         RGBA8) in the context's chain slot, valid until that slot is written again.  layers_or_ptrs / on_device as downscale_rgba_batch_dev."""
-        items = list(layers_or_ptrs); n = len(items)
-        if on_device is None:
-            on_device = n > 0 and all(isinstance(x, int) for x in items)
-        keep = []
-        if on_device:
-            ptrs = (C.c_void_p * n)(*[int(p) if p else None for p in items])
-        else:
-            for a in items:
-                if a is None:
-                    keep.append(None); continue
-                a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
-                if a.size != width * height * 4:
-                    raise ValueError("every layer must hold width * height * 4 bytes")
-                keep.append(a)
-            ptrs = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep])
+        ptrs, keep, on_device = _layers(layers_or_ptrs, width, height, on_device); n = len(ptrs)
         full = max(self.mip_level_count(width, height), 1)
         nl = levels if 1 <= levels <= full else full          # (the array is sized for the longest chain; the library judges `levels`)
         out = (C.c_void_p * max(n * (full - 1), 1))()
@@ -446,21 +451,7 @@ class Codec:
         uploaded; on_device=None: device pointers when every entry is an int.  Returns a list of [by, bx, 8] uint8 arrays - or, with
         out_dev_ptrs (one 8-byte aligned device buffer of uvol_etc2_rgb_bound bytes per layer), writes there and returns None.  layer_cap:
         the size of each output buffer when it is not the bound."""
-        items = list(layers_or_ptrs); n = len(items)
-        if on_device is None:
-            on_device = n > 0 and all(isinstance(x, int) for x in items)
-        keep = []
-        if on_device:
-            ptrs = (C.c_void_p * n)(*[int(p) if p else None for p in items])
-        else:
-            for a in items:
-                if a is None:
-                    keep.append(None); continue
-                a = np.ascontiguousarray(np.frombuffer(a, np.uint8) if isinstance(a, (bytes, bytearray)) else a, dtype=np.uint8)
-                if a.size != width * height * 4:
-                    raise ValueError("every layer must hold width * height * 4 bytes")
-                keep.append(a)
-            ptrs = (C.c_void_p * n)(*[a.ctypes.data if a is not None else None for a in keep])
+        ptrs, keep, on_device = _layers(layers_or_ptrs, width, height, on_device); n = len(ptrs)
         bx, by = (width + 3) // 4, (height + 3) // 4
         cap = bx * by * 8 if layer_cap is None else layer_cap
         if out_dev_ptrs is not None:
@@ -487,16 +478,8 @@ class Codec:
         meshes = (Mesh * n)(); keep = []; fms = []
         for i, f in enumerate(frames):
             m, k, fm = self._mesh_host_mat(**f); meshes[i] = m; keep.append(k); fms.append(fm)
-        caps = (C.c_size_t * n)(); lens = (C.c_size_t * n)(); st = (C.c_int * n)(); outs = (C.c_void_p * n)()
-        bufs = [] if slot is None else self.__dict__.setdefault("_slot_bufs", {}).setdefault(("host", slot), [])
-        while len(bufs) < n:
-            bufs.append(np.empty(0, dtype=np.uint8))
-        mats = self._mat_ptrs(fms)
-        for i in range(n):
-            cap = (self.L.uvol_mesh_bound if mats is None else self.L.uvol_mesh_bound_mat)(C.byref(meshes[i]))
-            if bufs[i].size < cap:
-                bufs[i] = np.empty(cap, dtype=np.uint8)
-            caps[i] = cap; outs[i] = bufs[i].ctypes.data
+        mats = self._mat_ptrs(fms); lens = (C.c_size_t * n)(); st = (C.c_int * n)()
+        bufs, outs, caps = self._slot_bufs(None if slot is None else ("mesh", "host", slot), n, self.L.uvol_mesh_bound if mats is None else self.L.uvol_mesh_bound_mat, meshes)
         if mats is None:
             rc = self.L.uvol_encode_mesh_batch_async(self.h, meshes, n, outs, caps, lens, st)
         else:
@@ -509,41 +492,31 @@ class Codec:
         """Enqueues uvol_encode_mesh_batch_dev_async for a ctypes array of Mesh holding DEVICE pointers.  The output buffers of `slot`
         are re-used by every call with that slot (two slots let consecutive enqueued calls overlap without a buffer set per call);
         finish() returns numpy views into them."""
-        n = len(meshes)
-        sets = self.__dict__.setdefault("_slot_bufs", {})
-        bufs = sets.setdefault(slot, [])
-        while len(bufs) < n:
-            bufs.append(np.empty(0, dtype=np.uint8))
-        caps = (C.c_size_t * n)(); lens = (C.c_size_t * n)(); st = (C.c_int * n)(); outs = (C.c_void_p * n)()
-        for i in range(n):
-            cap = self.L.uvol_mesh_bound(C.byref(meshes[i]))
-            if bufs[i].size < cap:
-                bufs[i] = np.empty(cap, dtype=np.uint8)
-            caps[i] = cap; outs[i] = bufs[i].ctypes.data
+        n = len(meshes); lens = (C.c_size_t * n)(); st = (C.c_int * n)()
+        bufs, outs, caps = self._slot_bufs(("mesh", "dev", slot), n, self.L.uvol_mesh_bound, meshes)
         rc = self.L.uvol_encode_mesh_batch_dev_async(self.h, meshes, n, outs, caps, lens, st)
         if rc != UVOL_OK:
             raise UvolError(f"encode_mesh_batch_dev_async rc={rc}: {self.error()}")
         self._pending = getattr(self, "_pending", []) + [("mesh_views", n, bufs, lens, st, (caps, outs), meshes)]
 
-    def _tex_bufs(self, slot, nseg, cap):
-        """Output buffers of texture slot `slot` (kept between calls: no fresh pages to fault in per batch)."""
-        bufs = self.__dict__.setdefault("_slot_bufs", {}).setdefault(("tex", slot), [])
-        while len(bufs) < nseg:
+    def _slot_bufs(self, key, n, bound=None, meshes=None, cap=None):
+        """The output arguments of a batch call: n buffers of the set `key`, which is kept between calls and re-used by every call with that key
+        (no fresh pages to fault in per batch; None: fresh buffers), each grown to bound(meshes[i]) - meshes - or to `cap` - textures.
+        -> (the buffers, the void* array, the capacity array)"""
+        bufs = [] if key is None else self.__dict__.setdefault("_out_bufs", {}).setdefault(key, [])
+        while len(bufs) < n:
             bufs.append(np.empty(0, dtype=np.uint8))
-        for i in range(nseg):
-            if bufs[i].size < cap:
-                bufs[i] = np.empty(cap, dtype=np.uint8)
-        return bufs
+        caps = (C.c_size_t * n)(); outs = (C.c_void_p * n)()
+        for i, c in enumerate([cap] * n if bound is None else [bound(C.byref(meshes[i])) for i in range(n)]):
+            if bufs[i].size < c:
+                bufs[i] = np.empty(c, dtype=np.uint8)
+            caps[i] = c; outs[i] = bufs[i].ctypes.data
+        return bufs, outs, caps
 
     def start_texture_segments(self, segments, slot=None):
         """Enqueues uvol_encode_texture_segments_async for host segments (slot: as in start_mesh_batch)."""
-        arrs = [[np.ascontiguousarray(a, dtype=np.uint8) for a in seg] for seg in segments]
-        h, w = arrs[0][0].shape[:2]; nl = len(arrs[0]); nseg = len(arrs)
-        flat = [a for seg in arrs for a in seg]
-        ptrs = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
-        cap = self.L.uvol_texture_bound(w, h, nl)
-        bufs = [np.empty(cap, dtype=np.uint8) for _ in range(nseg)] if slot is None else self._tex_bufs(slot, nseg, cap)
-        outs = (C.c_void_p * nseg)(*[b.ctypes.data for b in bufs[:nseg]]); caps = (C.c_size_t * nseg)(*([cap] * nseg)); lens = (C.c_size_t * nseg)()
+        flat, ptrs, w, h, nl, nseg = _segments(segments); lens = (C.c_size_t * nseg)()
+        bufs, outs, caps = self._slot_bufs(None if slot is None else ("tex", slot), nseg, cap=self.L.uvol_texture_bound(w, h, nl))
         rc = self.L.uvol_encode_texture_segments_async(self.h, ptrs, nseg, nl, w, h, outs, caps, lens)
         if rc != UVOL_OK:
             raise UvolError(f"encode_texture_segments_async rc={rc}: {self.error()}")
@@ -552,10 +525,8 @@ class Codec:
     def start_texture_segments_dev(self, dev_ptrs, n_layers, width, height, slot=0):
         """Enqueues uvol_encode_texture_segments_dev_async for a flat list of n_segments * n_layers DEVICE pointers; output buffers of `slot`
         are re-used, finish() returns numpy views."""
-        ptrs = (C.c_void_p * len(dev_ptrs))(*[int(p) for p in dev_ptrs]); nseg = len(dev_ptrs) // n_layers
-        cap = self.L.uvol_texture_bound(width, height, n_layers)
-        bufs = self._tex_bufs(("dev", slot), nseg, cap)
-        outs = (C.c_void_p * nseg)(*[b.ctypes.data for b in bufs[:nseg]]); caps = (C.c_size_t * nseg)(*([cap] * nseg)); lens = (C.c_size_t * nseg)()
+        ptrs = (C.c_void_p * len(dev_ptrs))(*[int(p) for p in dev_ptrs]); nseg = len(dev_ptrs) // n_layers; lens = (C.c_size_t * nseg)()
+        bufs, outs, caps = self._slot_bufs(("tex", "dev", slot), nseg, cap=self.L.uvol_texture_bound(width, height, n_layers))
         rc = self.L.uvol_encode_texture_segments_dev_async(self.h, ptrs, nseg, n_layers, width, height, outs, caps, lens)
         if rc != UVOL_OK:
             raise UvolError(f"encode_texture_segments_dev_async rc={rc}: {self.error()}")
@@ -591,17 +562,8 @@ class Codec:
         return res
 
     def _run_batch(self, fn, meshes, n, raise_on_error, views=False, bound=None):
-        bound = bound or self.L.uvol_mesh_bound
-        caps = (C.c_size_t * n)(); lens = (C.c_size_t * n)(); st = (C.c_int * n)(); outs = (C.c_void_p * n)()
-        bufs = getattr(self, "_obufs", [])          # output buffers are kept between calls (no fresh pages to fault in per batch)
-        while len(bufs) < n:
-            bufs.append(np.empty(0, dtype=np.uint8))
-        for i in range(n):
-            cap = bound(C.byref(meshes[i]))
-            if bufs[i].size < cap:
-                bufs[i] = np.empty(cap, dtype=np.uint8)
-            caps[i] = cap; outs[i] = bufs[i].ctypes.data
-        self._obufs = bufs
+        lens = (C.c_size_t * n)(); st = (C.c_int * n)()
+        bufs, outs, caps = self._slot_bufs(("mesh", "blocking"), n, bound or self.L.uvol_mesh_bound, meshes)
         rc = fn(self.h, meshes, n, outs, caps, lens, st)
         if rc != UVOL_OK:
             raise UvolError(f"encode_mesh_batch rc={rc}: {self.error()}")
@@ -635,13 +597,8 @@ class Codec:
     def encode_texture_segments(self, segments, views=False):
         """segments: list of lists of HxWx4 uint8 arrays (same size, same layer count) -> list of .ktx2 bytes (one batched call;
         views=True: numpy views of this codec's output buffers, valid until the next call)."""
-        arrs = [[np.ascontiguousarray(a, dtype=np.uint8) for a in seg] for seg in segments]
-        h, w = arrs[0][0].shape[:2]; nl = len(arrs[0])
-        flat = [a for seg in arrs for a in seg]
-        if any(len(seg) != nl for seg in arrs) or any(a.shape != (h, w, 4) for a in flat):
-            raise ValueError("all segments must have the same layer count and HxWx4 size")
-        ptrs = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
-        return self._run_tex_batch(self.L.uvol_encode_texture_segments, ptrs, len(arrs), nl, w, h, views)
+        flat, ptrs, w, h, nl, nseg = _segments(segments)
+        return self._run_tex_batch(self.L.uvol_encode_texture_segments, ptrs, nseg, nl, w, h, views)
 
     def encode_texture_segments_dev(self, dev_ptrs, n_layers, width, height, views=False):
         """dev_ptrs: flat list of n_segments*n_layers device pointers."""
@@ -651,17 +608,19 @@ class Codec:
     def encode_texture_segments_status(self, segments, caps=None):
         """Per-segment results (uvol_encode_texture_segments_st): -> (list of .ktx2 bytes or None, list of status codes).  caps: optional
         output capacities per segment (tests: a too-small one fails alone with UVOL_E_NOSPACE)."""
-        arrs = [[np.ascontiguousarray(a, dtype=np.uint8) for a in seg] for seg in segments]
-        h, w = arrs[0][0].shape[:2]; nl = len(arrs[0]); nseg = len(arrs)
-        flat = [a for seg in arrs for a in seg]
-        ptrs = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
-        cap = self.L.uvol_texture_bound(w, h, nl)
+        flat, ptrs, w, h, nl, nseg = _segments(segments)
+        run = lambda outs, capa, lens, st: self.L.uvol_encode_texture_segments_st(self.h, ptrs, nseg, nl, w, h, 0, outs, capa, lens, st)
+        return self._run_tex_st(run, "encode_texture_segments_st", nseg, self.L.uvol_texture_bound(w, h, nl), caps)
+
+    def _run_tex_st(self, run, name, nseg, cap, caps):
+        """The per-segment texture encode forms: fresh output buffers of `cap` bytes (or the caller's `caps`) -> (list of .ktx2 bytes or None,
+        list of status codes)."""
         cl = [cap] * nseg if caps is None else [int(c) for c in caps]
         bufs = [np.empty(max(c, 1), dtype=np.uint8) for c in cl]
         outs = (C.c_void_p * nseg)(*[b.ctypes.data for b in bufs]); capa = (C.c_size_t * nseg)(*cl); lens = (C.c_size_t * nseg)(); st = (C.c_int * nseg)()
-        rc = self.L.uvol_encode_texture_segments_st(self.h, ptrs, nseg, nl, w, h, 0, outs, capa, lens, st)
+        rc = run(outs, capa, lens, st)
         if rc != UVOL_OK:
-            raise UvolError(f"encode_texture_segments_st rc={rc}: {self.error()}")
+            raise UvolError(f"{name} rc={rc}: {self.error()}")
         return [bufs[i][:lens[i]].tobytes() if st[i] == UVOL_OK else None for i in range(nseg)], list(st)
 
     def encode_texture_segments_mips(self, segments, levels=0, caps=None, dev_ptrs=None, shape=None):
@@ -672,18 +631,9 @@ class Codec:
             w, h, nl = shape; flat = [int(p) for p in dev_ptrs]; nseg = len(flat) // nl
             ptrs = (C.c_void_p * len(flat))(*flat)
         else:
-            arrs = [[np.ascontiguousarray(a, dtype=np.uint8) for a in seg] for seg in segments]
-            h, w = arrs[0][0].shape[:2]; nl = len(arrs[0]); nseg = len(arrs)
-            flat = [a for seg in arrs for a in seg]
-            ptrs = (C.c_void_p * len(flat))(*[a.ctypes.data for a in flat])
-        cap = self.L.uvol_texture_bound_mips(w, h, nl, levels) or self.L.uvol_texture_bound(w, h, nl)
-        cl = [cap] * nseg if caps is None else [int(c) for c in caps]
-        bufs = [np.empty(max(c, 1), dtype=np.uint8) for c in cl]
-        outs = (C.c_void_p * nseg)(*[b.ctypes.data for b in bufs]); capa = (C.c_size_t * nseg)(*cl); lens = (C.c_size_t * nseg)(); st = (C.c_int * nseg)()
-        rc = self.L.uvol_encode_texture_segments_mips(self.h, ptrs, nseg, nl, w, h, 0 if dev_ptrs is None else 1, levels, outs, capa, lens, st)
-        if rc != UVOL_OK:
-            raise UvolError(f"encode_texture_segments_mips rc={rc}: {self.error()}")
-        return [bufs[i][:lens[i]].tobytes() if st[i] == UVOL_OK else None for i in range(nseg)], list(st)
+            flat, ptrs, w, h, nl, nseg = _segments(segments)
+        run = lambda outs, capa, lens, st: self.L.uvol_encode_texture_segments_mips(self.h, ptrs, nseg, nl, w, h, 0 if dev_ptrs is None else 1, levels, outs, capa, lens, st)
+        return self._run_tex_st(run, "encode_texture_segments_mips", nseg, self.L.uvol_texture_bound_mips(w, h, nl, levels) or self.L.uvol_texture_bound(w, h, nl), caps)
 
     def ktx2_levels(self, data: bytes):
         """uvol_ktx2_levels: the mip level count of a .ktx2 this codec reads (1 for an ETC1S file)."""
@@ -700,7 +650,7 @@ class Codec:
         unreadable or corrupt ones -> (list of arrays or None, list of status codes).  shape = (w, h, layers) if the first file is not readable.
         level: the mip level asked of every file (uvol_transcode_texture_segments_level): the arrays have the LEVEL's size; shape stays the
         files' level-0 shape."""
-        files = [bytes(f) for f in files]; n = len(files)
+        files, fp, ln, n = _files(files); st = (C.c_int * n)()
         code, unit, blocks = self.TARGETS[target]
         if shape is None:
             for f in files:
@@ -713,7 +663,6 @@ class Codec:
             w, h = max(1, w >> level), max(1, h >> level)
         bx, by = (w + 3) // 4, (h + 3) // 4
         outs = [np.zeros((nl, by, bx, unit) if blocks else (nl, h, w, 4), dtype=np.uint8) for _ in range(n)]
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
         ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
         if level is None:
             rc = self.L.uvol_transcode_texture_segments_st(self.h, fp, ln, n, ptrs, bx * by * unit if blocks else w * h * 4, 0, code, st)
@@ -724,9 +673,7 @@ class Codec:
         return [outs[i] if st[i] == UVOL_OK else None for i in range(n)], list(st)
 
     def _run_tex_batch(self, fn, ptrs, nseg, nl, w, h, views=False):
-        cap = self.L.uvol_texture_bound(w, h, nl)
-        bufs = self._tex_bufs("blocking", nseg, cap)
-        outs = (C.c_void_p * nseg)(*[b.ctypes.data for b in bufs[:nseg]]); caps = (C.c_size_t * nseg)(*([cap] * nseg)); lens = (C.c_size_t * nseg)()
+        bufs, outs, caps = self._slot_bufs(("tex", "blocking"), nseg, cap=self.L.uvol_texture_bound(w, h, nl)); lens = (C.c_size_t * nseg)()
         rc = fn(self.h, ptrs, nseg, nl, w, h, outs, caps, lens)
         if rc != UVOL_OK:
             raise UvolError(f"encode_texture_segments rc={rc}: {self.error()}")
@@ -751,68 +698,45 @@ class Codec:
     def decode_texture_segments(self, files, out=None):
         """files: list of .ktx2 bytes (one width / height / layer count) -> list (per segment) of [layers, H, W, 4] uint8 arrays,
         rows in stored order (the encoder's -y_flip is part of the stored image)."""
-        files = [bytes(f) for f in files]
-        w, h, nl = self.ktx2_info(files[0]); n = len(files)
+        files, fp, ln, n = _files(files)
+        w, h, nl = self.ktx2_info(files[0])
         outs = out if out is not None else [np.empty((nl, h, w, 4), dtype=np.uint8) for _ in range(n)]      # out: arrays of an earlier call, re-used
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files])
         ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
         rc = self.L.uvol_decode_texture_segments(self.h, fp, ln, n, ptrs, w * h * 4)
         if rc != UVOL_OK:
             raise UvolError(f"decode_texture_segments rc={rc}: {self.error()}")
         return outs
 
+    def _transcode(self, files, entry, unit, name):
+        """The single-target transcode methods: -> list (per segment) of [layers, by, bx, unit] uint8 arrays of 4x4 blocks (raster order)."""
+        files, fp, ln, n = _files(files)
+        w, h, nl = self.ktx2_info(files[0]); bx, by = (w + 3) // 4, (h + 3) // 4
+        outs = [np.empty((nl, by, bx, unit), dtype=np.uint8) for _ in range(n)]
+        ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
+        rc = entry(self.h, fp, ln, n, ptrs, bx * by * unit, 0)
+        if rc != UVOL_OK:
+            raise UvolError(f"{name} rc={rc}: {self.error()}")
+        return outs
+
     def transcode_texture_segments_etc1(self, files):
         """files: list of .ktx2 bytes -> list (per segment) of [layers, by, bx, 8] uint8 arrays of ETC1 blocks (raster order)."""
-        files = [bytes(f) for f in files]
-        w, h, nl = self.ktx2_info(files[0]); n = len(files); bx, by = (w + 3) // 4, (h + 3) // 4
-        outs = [np.empty((nl, by, bx, 8), dtype=np.uint8) for _ in range(n)]
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files])
-        ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
-        rc = self.L.uvol_transcode_texture_segments_etc1(self.h, fp, ln, n, ptrs, bx * by * 8, 0)
-        if rc != UVOL_OK:
-            raise UvolError(f"transcode_texture_segments_etc1 rc={rc}: {self.error()}")
-        return outs
+        return self._transcode(files, self.L.uvol_transcode_texture_segments_etc1, 8, "transcode_texture_segments_etc1")
 
     def transcode_texture_segments_bc7(self, files):
         """files: list of .ktx2 bytes -> list (per segment) of [layers, by, bx, 16] uint8 arrays of BC7 mode-6 blocks (raster order)."""
-        files = [bytes(f) for f in files]
-        w, h, nl = self.ktx2_info(files[0]); n = len(files); bx, by = (w + 3) // 4, (h + 3) // 4
-        outs = [np.empty((nl, by, bx, 16), dtype=np.uint8) for _ in range(n)]
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files])
-        ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
-        rc = self.L.uvol_transcode_texture_segments_bc7(self.h, fp, ln, n, ptrs, bx * by * 16, 0)
-        if rc != UVOL_OK:
-            raise UvolError(f"transcode_texture_segments_bc7 rc={rc}: {self.error()}")
-        return outs
+        return self._transcode(files, self.L.uvol_transcode_texture_segments_bc7, 16, "transcode_texture_segments_bc7")
 
     def transcode_texture_segments_etc2_rgba(self, files):
         """files: list of .ktx2 bytes (with or without alpha slices) -> list (per segment) of [layers, by, bx, 16] uint8 arrays of ETC2 RGBA blocks."""
-        files = [bytes(f) for f in files]
-        w, h, nl = self.ktx2_info(files[0]); n = len(files); bx, by = (w + 3) // 4, (h + 3) // 4
-        outs = [np.empty((nl, by, bx, 16), dtype=np.uint8) for _ in range(n)]
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files])
-        ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
-        rc = self.L.uvol_transcode_texture_segments_etc2_rgba(self.h, fp, ln, n, ptrs, bx * by * 16, 0)
-        if rc != UVOL_OK:
-            raise UvolError(f"transcode_texture_segments_etc2_rgba rc={rc}: {self.error()}")
-        return outs
+        return self._transcode(files, self.L.uvol_transcode_texture_segments_etc2_rgba, 16, "transcode_texture_segments_etc2_rgba")
 
     def transcode_texture_segments_astc(self, files):
         """files: list of UASTC .ktx2 bytes -> list (per segment) of [layers, by, bx, 16] uint8 arrays of ASTC 4x4 blocks (raster order)."""
-        files = [bytes(f) for f in files]
-        w, h, nl = self.ktx2_info(files[0]); n = len(files); bx, by = (w + 3) // 4, (h + 3) // 4
-        outs = [np.empty((nl, by, bx, 16), dtype=np.uint8) for _ in range(n)]
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files])
-        ptrs = (C.c_void_p * (n * nl))(*[outs[s][l].ctypes.data for s in range(n) for l in range(nl)])
-        rc = self.L.uvol_transcode_texture_segments_astc(self.h, fp, ln, n, ptrs, bx * by * 16, 0)
-        if rc != UVOL_OK:
-            raise UvolError(f"transcode_texture_segments_astc rc={rc}: {self.error()}")
-        return outs
+        return self._transcode(files, self.L.uvol_transcode_texture_segments_astc, 16, "transcode_texture_segments_astc")
 
     def decode_texture_segments_dev(self, files, dev_ptrs, layer_cap):
         """Same, into caller-owned device buffers: dev_ptrs = flat list of n_segments*layers device pointers."""
-        files = [bytes(f) for f in files]; n = len(files)
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files])
+        files, fp, ln, n = _files(files)
         ptrs = (C.c_void_p * len(dev_ptrs))(*[int(p) for p in dev_ptrs])
         rc = self.L.uvol_decode_texture_segments_dev(self.h, fp, ln, n, ptrs, layer_cap)
         if rc != UVOL_OK:
@@ -837,7 +761,7 @@ class Codec:
         (uvol_decode_mesh_batch_mat: one more kernel and one more array per frame; size an arena with decode_arena_bytes(files, materials=True)).
         arena (a PinnedArena, with views=True): the output arrays are carved from it - outputs that all lie in uvol_host_alloc memory are written
         by the DMA engines where they are, without the library's staging buffers."""
-        files = [bytes(f) for f in files]; n = len(files)
+        files, fp, ln, n = _files(files); st = (C.c_int * n)()
         metas = (DecodedMesh * n)(); keep = []
         pool = self.__dict__.setdefault("_dec_bufs_pinned" if arena is not None else "_dec_bufs", []) if views else None      # views=True: the arrays are kept and re-used by the next call
         mk = (lambda shape, dt: arena.take(shape, dt)) if arena is not None else (lambda shape, dt: np.empty(shape, dt))
@@ -858,7 +782,6 @@ class Codec:
             m = metas[i]; m.cap_faces = nf.value; m.cap_values = mv.value
             for k, v in a.items():
                 setattr(m, k, v.ctypes.data if fetch else None)        # fetch=False: decode only, results stay on the device (timing)
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
         fmats = None; hm = (C.c_int * n)()
         if fetch and materials:                # (with an arena the ids lie in it too: one pageable output would send the whole call through the staging buffers)
             fmats = [mk((max(1, metas[i].cap_faces),), np.uint8) for i in range(n)]
@@ -902,57 +825,68 @@ class Codec:
         arrays stay in HBM and the call returns the statuses, the counts are in `metas`.  A failed frame is None (raise_on_error=False); a
         foreign file or a frame that does not fit fails alone.  status_out (a list): receives the per-frame codes of a host-output call; with
         `metas` (capacities of the caller's choosing, arrays allocated here) n_points / n_faces of a frame that did not fit are the needed counts."""
-        files = [bytes(f) for f in files]; n = len(files)
         lay = {"planar": UVOL_POINTS_PLANAR, "interleaved": UVOL_POINTS_INTERLEAVED}[layout]
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
-        if on_device:
-            if metas is None:
-                raise UvolError("decode_mesh_batch_points(on_device=True) takes the caller's device buffers in `metas`")
+        if on_device and metas is not None:
             for m in metas:
                 m.layout = lay
-            rc = self.L.uvol_decode_mesh_batch_points(self.h, fp, ln, n, 1, metas, st)
-            if rc != UVOL_OK:
-                raise UvolError(f"decode_mesh_batch_points rc={rc}: {self.error()}")
-            return list(st)
-        own = metas is None
-        if own:
-            metas = (DecodedPoints * n)()
-        mk = (lambda shape, dt: arena.take(shape, dt)) if arena is not None else (lambda shape, dt: np.empty(shape, dt))
-        keep = []
-        for i, f in enumerate(files):
-            m = metas[i]; a = {}
-            if own:
-                nf, mv = C.c_uint32(), C.c_uint32()
-                ok = self.L.uvol_drc_info(f, len(f), C.byref(nf), C.byref(mv)) == UVOL_OK      # (a foreign file fails in its own slot below)
-                m.cap_faces = nf.value if ok else 0; m.cap_points = mv.value if ok else 0
+
+        def attach(m, cp, cf, mk):
             m.layout = lay
-            cp, cf = max(1, int(m.cap_points)), max(1, int(m.cap_faces))
-            a["index"] = mk((3 * cf,), np.uint32)
+            a = dict(index=mk((3 * cf,), np.uint32))
             if lay == UVOL_POINTS_INTERLEAVED:
                 a["points"] = mk((cp, 8), np.float32); m.pos = a["points"].ctypes.data; m.uv = None; m.nrm = None
             else:
                 a["pos"] = mk((cp, 3), np.float32); a["uv"] = mk((cp, 2), np.float32); a["nrm"] = mk((cp, 3), np.float32)
                 m.pos, m.uv, m.nrm = a["pos"].ctypes.data, a["uv"].ctypes.data, a["nrm"].ctypes.data
             m.index = a["index"].ctypes.data
-            keep.append(a)
-        rc = self.L.uvol_decode_mesh_batch_points(self.h, fp, ln, n, 0, metas, st)
+            return a
+
+        def result(m, a):
+            npnt = m.n_points
+            r = dict(index=a["index"][:3 * m.n_faces], n_faces=m.n_faces, n_points=npnt, has_uv=bool(m.has_uv), has_nrm=bool(m.has_nrm))
+            if lay == UVOL_POINTS_INTERLEAVED:
+                r["points"] = a["points"][:npnt]
+            else:
+                r["pos"] = a["pos"][:npnt]; r["uv"] = a["uv"][:npnt] if m.has_uv else None; r["nrm"] = a["nrm"][:npnt] if m.has_nrm else None
+            return r
+        return self._decode_welded("decode_mesh_batch_points", self.L.uvol_decode_mesh_batch_points, DecodedPoints, attach, result,
+                                   files, on_device, arena, raise_on_error, metas, status_out)
+
+    def _decode_welded(self, name, entry, struct, attach, result, files, on_device, arena, raise_on_error, metas, status_out):
+        """The render-ready decode methods.  attach(m, cap_points, cap_faces, mk) allocates one frame's output arrays with mk(shape, dtype) and
+        sets m's pointers -> the arrays; result(m, arrays) is a decoded frame's dict."""
+        files, fp, ln, n = _files(files); st = (C.c_int * n)()
+        if on_device:
+            if metas is None:
+                raise UvolError(f"{name}(on_device=True) takes the caller's device buffers in `metas`")
+            rc = entry(self.h, fp, ln, n, 1, metas, st)
+            if rc != UVOL_OK:
+                raise UvolError(f"{name} rc={rc}: {self.error()}")
+            return list(st)
+        own = metas is None
+        if own:
+            metas = (struct * n)()
+        mk = (lambda shape, dt: arena.take(shape, dt)) if arena is not None else (lambda shape, dt: np.empty(shape, dt))
+        keep = []
+        for i, f in enumerate(files):
+            m = metas[i]
+            if own:
+                nf, mv = C.c_uint32(), C.c_uint32()
+                ok = self.L.uvol_drc_info(f, len(f), C.byref(nf), C.byref(mv)) == UVOL_OK      # (a foreign file fails in its own slot below)
+                m.cap_faces = nf.value if ok else 0; m.cap_points = mv.value if ok else 0
+            keep.append(attach(m, max(1, int(m.cap_points)), max(1, int(m.cap_faces)), mk))
+        rc = entry(self.h, fp, ln, n, 0, metas, st)
         if status_out is not None:
             status_out[:] = list(st)
         if rc != UVOL_OK:
-            raise UvolError(f"decode_mesh_batch_points rc={rc}: {self.error()}")
+            raise UvolError(f"{name} rc={rc}: {self.error()}")
         res = []
         for i in range(n):
             if st[i] != UVOL_OK:
                 if raise_on_error:
                     raise UvolError(f"frame {i} failed status={st[i]}: {self.error()}")
                 res.append(None); continue
-            m, a = metas[i], keep[i]; npnt = m.n_points
-            r = dict(index=a["index"][:3 * m.n_faces], n_faces=m.n_faces, n_points=npnt, has_uv=bool(m.has_uv), has_nrm=bool(m.has_nrm))
-            if lay == UVOL_POINTS_INTERLEAVED:
-                r["points"] = a["points"][:npnt]
-            else:
-                r["pos"] = a["pos"][:npnt]; r["uv"] = a["uv"][:npnt] if m.has_uv else None; r["nrm"] = a["nrm"][:npnt] if m.has_nrm else None
-            res.append(r)
+            res.append(result(metas[i], keep[i]))
         return res
 
     def decode_mesh_batch_packed(self, files, on_device=False, arena=None, raise_on_error=True, metas=None, status_out=None):
@@ -963,43 +897,13 @@ class Codec:
         decode_mesh_batch_points, except in a frame whose material is a corner attribute (interior material seams): there the corner's material
         is part of the point tuple, and a point shared by two materials becomes one point per material.  The other arguments are those of decode_mesh_batch_points, `metas` a (PackedPoints * n) array; a
         PinnedArena of points_arena_bytes(files) is large enough."""
-        files = [bytes(f) for f in files]; n = len(files)
-        fp = (C.c_char_p * n)(*files); ln = (C.c_size_t * n)(*[len(f) for f in files]); st = (C.c_int * n)()
-        if on_device:
-            if metas is None:
-                raise UvolError("decode_mesh_batch_packed(on_device=True) takes the caller's device buffers in `metas`")
-            rc = self.L.uvol_decode_mesh_batch_packed(self.h, fp, ln, n, 1, metas, st)
-            if rc != UVOL_OK:
-                raise UvolError(f"decode_mesh_batch_packed rc={rc}: {self.error()}")
-            return list(st)
-        own = metas is None
-        if own:
-            metas = (PackedPoints * n)()
-        mk = (lambda shape, dt: arena.take(shape, dt)) if arena is not None else (lambda shape, dt: np.empty(shape, dt))
-        keep = []
-        for i, f in enumerate(files):
-            m = metas[i]
-            if own:
-                nf, mv = C.c_uint32(), C.c_uint32()
-                ok = self.L.uvol_drc_info(f, len(f), C.byref(nf), C.byref(mv)) == UVOL_OK      # (a foreign file fails in its own slot below)
-                m.cap_faces = nf.value if ok else 0; m.cap_points = mv.value if ok else 0
-            cp, cf = max(1, int(m.cap_points)), max(1, int(m.cap_faces))
+        def attach(m, cp, cf, mk):
             a = dict(index=mk((3 * cf,), np.uint32), records=mk((cp, 16), np.uint8))
             m.records = a["records"].ctypes.data; m.index = a["index"].ctypes.data
-            keep.append(a)
-        rc = self.L.uvol_decode_mesh_batch_packed(self.h, fp, ln, n, 0, metas, st)
-        if status_out is not None:
-            status_out[:] = list(st)
-        if rc != UVOL_OK:
-            raise UvolError(f"decode_mesh_batch_packed rc={rc}: {self.error()}")
-        res = []
-        for i in range(n):
-            if st[i] != UVOL_OK:
-                if raise_on_error:
-                    raise UvolError(f"frame {i} failed status={st[i]}: {self.error()}")
-                res.append(None); continue
-            res.append(dict(packed_meta(metas[i]), index=keep[i]["index"][:3 * metas[i].n_faces], records=keep[i]["records"][:metas[i].n_points].view(PACKED_RECORD).reshape(-1)))
-        return res
+            return a
+        result = lambda m, a: dict(packed_meta(m), index=a["index"][:3 * m.n_faces], records=a["records"][:m.n_points].view(PACKED_RECORD).reshape(-1))
+        return self._decode_welded("decode_mesh_batch_packed", self.L.uvol_decode_mesh_batch_packed, PackedPoints, attach, result,
+                                   files, on_device, arena, raise_on_error, metas, status_out)
 
     # ---- measurement ----
     def profile(self, on=True):
